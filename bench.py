@@ -10,6 +10,7 @@ already resident in HBM (one pristine copy per step is prepared before the
 timed region, so no copy is timed).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--n 8192] [--dtype f64] [--band 32]
+                    [--dump-outputs DIR] [--full]
 
 N > 1: one process per GPU.  Launched by torch.distributed.run (WORLD_SIZE
 set) it joins that job; run plainly as `python bench.py --gpus N` it starts
@@ -29,21 +30,28 @@ stage-1 streams ("lanes", matrix j on lane j mod L; one GPU: K dealt in
 balanced rounds of at most 10, plan_lanes) and ceil(L / 2) stage-2 streams
 (matrix j's stage 2 on stream j mod that, after its stage 1, beside the
 following matrices' stage 1; `--pipeline on`, the default), fill and drain
-inside the timed region.  The same K steps one reduction at a
-time on one lane (the reference's per-instance timing, timing.h:79-82) are
-reported as `one_at_a_time`, and `latency_ms_per_reduction` is one matrix's
+inside the timed region.  `latency_ms_per_reduction` is one matrix's
 stage 1 + stage 2 under overlap.  After every timed region the library's
 sticky stage-2 error words are read (brd_check_errors): a stalled sweep
 fails the run instead of being timed.
 
-Rank 0 prints ONE JSON line.  `value` comes from K timed steps with no
-per-launch instrumentation; K more steps one at a time are then run with the
-library's per-launch events (for the stage-1 apply stamped by the launch
-itself, hipExtLaunchKernel) for the dominant kernel's roofline object.  Also
-the CPU baseline: the reference's own tiled algorithm (built from its
-sources by oracle/Makefile) timed on this host at N = 320, 640, 1024 (about
-10-20 s) and 2048, extrapolated cubically from the largest sample to the GPU
-problem size (labelled as such).
+Rank 0 prints ONE JSON line.  `value` and `ms_per_step` come from K timed
+steps with no per-launch instrumentation, and a plain run does no more than
+that: set up, W warmup steps, the K timed steps, the line.
+--dump-outputs DIR then also writes what the last timed step computed
+(dump_outputs; every step starts from the same seeded matrix, so two builds
+can be compared output for output).
+
+--full adds, after the timed steps: the same K steps one reduction at a time
+on one lane (the reference's per-instance timing, timing.h:79-82), reported
+as `one_at_a_time`; K more steps one at a time with the library's per-launch
+events (for the stage-1 apply stamped by the launch itself,
+hipExtLaunchKernel) for the dominant kernel's roofline object; across GPUs
+the one-GPU stream at the same size (`single_gpu_same_n`); and the CPU
+baseline: the reference's own tiled algorithm (built from its sources by
+oracle/Makefile) timed on this host at N = 320, 640, 1024 (about 10-20 s)
+and 2048, extrapolated cubically from the largest sample to the GPU problem
+size (labelled as such).
 """
 from __future__ import annotations
 
@@ -73,7 +81,8 @@ def parse():
                    help="matrix size (default 8192 on one GPU, BASELINE configs[2]; 16384 across GPUs, configs[4])")
     p.add_argument("--dtype", choices=["f64", "f32"], default="f64")
     p.add_argument("--band", type=int, default=32)
-    p.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto")
+    p.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto",
+                   help="--full: time the reference's CPU code on this host (auto) or leave it out")
     p.add_argument("--cpu-n", type=str, default="320,640,1024,2048",
                    help="CPU-baseline sample sizes (comma separated; the largest is the reported sample)")
     p.add_argument("--s2", choices=["compat", "sigma"], default="compat",
@@ -87,7 +96,7 @@ def parse():
     p.add_argument("--s2-cus", type=int, default=None,
                    help="pipelined: CUs reserved for stage 2 (default svdsolver_amd.overlap_cus(n))")
     p.add_argument("--one-at-a-time", choices=["on", "off"], default="on",
-                   help="pipelined, one GPU: also time K steps without the overlap (reported as one_at_a_time)")
+                   help="--full, pipelined, one GPU: also time K steps without the overlap (reported as one_at_a_time)")
     p.add_argument("--lanes", type=int, default=None,
                    help="pipelined: stage-1 streams, matrix j on lane j mod L (default: one GPU plan_lanes(K), "
                         "10 for K = 20; across GPUs 8, each lane with its own RCCL communicator)")
@@ -107,6 +116,12 @@ def parse():
                         "(single_gpu_same_n in the line)")
     p.add_argument("--force-dist", action="store_true",
                    help="run the distributed path even at world size 1 (launch through torch.distributed.run)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run everything else the benchmark measures: the same steps "
+                        "one at a time, the profiled pass behind the roofline objects, the one-GPU stream at the "
+                        "same size (N > 1) and the CPU baseline; without it only the headline figure is measured")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed as DIR/<name>.npy (dump_outputs)")
     return p.parse_args()
 
 
@@ -350,6 +365,31 @@ def stage2_roofline(sw, n, b, dtype, steps):
             "chain_bound_note": "about 4 dependent windows per sweep (lag-3 rule, DESIGN.md Stage 2)"}
 
 
+DUMP_SAMPLE = 1 << 20      # entries of the matrix written when the whole of it is too large
+DUMP_WHOLE_MAX = 32 << 20  # bytes up to which the whole matrix is written
+
+
+def dump_outputs(torch, A, dirname: str) -> None:
+    """--dump-outputs: what the timed path hands its caller for one step, the
+    matrix reduced in place (extract=False: no separate d and e), written as
+    .npy in the benchmark's precision: d.npy and e.npy, its diagonal and
+    superdiagonal (the bidiagonal), and matrix.npy, the whole n x n array --
+    or, above DUMP_WHOLE_MAX bytes, matrix_sample.npy: DUMP_SAMPLE entries at
+    positions drawn once from a fixed seed (the same for every run at this n)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    n = A.shape[0]
+    np.save(os.path.join(dirname, "d.npy"), torch.diagonal(A).cpu().numpy())
+    np.save(os.path.join(dirname, "e.npy"), torch.diagonal(A, 1).cpu().numpy())
+    if n * n * A.element_size() <= DUMP_WHOLE_MAX:
+        np.save(os.path.join(dirname, "matrix.npy"), A.cpu().numpy())
+    else:
+        flat = np.random.default_rng(8192).integers(0, n * n, size=DUMP_SAMPLE)
+        rows = torch.from_numpy(flat // n).to(A.device)
+        cols = torch.from_numpy(flat % n).to(A.device)
+        np.save(os.path.join(dirname, "matrix_sample.npy"), A[rows, cols].cpu().numpy())
+
+
 def plan_lanes(k: int, lmax: int = 10) -> int:
     """Stage-1 lanes for a stream of k matrices: the fewest rounds that
     lmax lanes allow, but at least two (the first round's sweeps then run
@@ -503,9 +543,10 @@ def main():
     tdt = torch.float64 if args.dtype == "f64" else torch.float32
     dist_mode = (world > 1 or args.force_dist) and args.mode == "dist"
     pipelined = args.pipeline == "on"
-    serial_too = pipelined and not dist_mode and args.one_at_a_time == "on"   # also time them one at a time
-    # warmup, the timed steps, the profiled steps (+ the one-at-a-time steps)
-    nmat = args.warmup + (3 if serial_too else 2) * args.steps
+    # --full: also time them one at a time
+    serial_too = args.full and pipelined and not dist_mode and args.one_at_a_time == "on"
+    # warmup and the timed steps; --full: the profiled steps (+ the one-at-a-time steps)
+    nmat = args.warmup + args.steps + ((2 if serial_too else 1) * args.steps if args.full else 0)
     mode = {"pipe": pipelined}
     s2_cus = S.overlap_cus(n) if pipelined else 0
     if args.s2_cus is not None:
@@ -662,37 +703,48 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if args.comm == "rccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:
+        # the last timed step's matrix, where it lies: on one GPU (and per
+        # replica) reduced in place, sharded on the rank that ran its stage 2
+        j = args.warmup + args.steps - 1
+        if dist_mode:
+            result = Bfull[band_of(j)] if rank == root_of(j) else None
+        else:
+            result = mats[j] if rank == 0 else None
+        if result is not None and args.steps > 0:
+            dump_outputs(torch, result, args.dump_outputs)
     one_at_a_time = None
-    if serial_too:
-        # (2) the same kind of steps without any overlap (one reduction at a
-        # time, whole chip per stage): the latency of one reduction, reported
-        # beside the stream's throughput
-        mode["pipe"] = False
-        S.set_overlap(0)
-        el_s, s1_s, s2_s = run_steps(args.warmup + args.steps)
-        one_at_a_time = {"value": round(args.steps * 8.0 / 3.0 * n ** 3 / el_s / 1e9, 2),
-                         "ms_per_step": round(el_s / args.steps * 1e3, 3),
-                         "stage_ms": {"stage1": round(s1_s, 3), "stage2": round(s2_s, 3)}}
-    # (3) K steps with the library's per-launch HIP events on its launch
-    # streams: kernel durations for the roofline object.  On one GPU they run
-    # one reduction at a time (as in (2)), so a kernel's duration is its own,
-    # not stretched by the concurrent lanes of (1); across GPUs they repeat (1).
-    S.profile_reset()
-    S.profile_enable(True)
-    el_prof, _, _ = run_steps(args.warmup + (2 if serial_too else 1) * args.steps)
-    S.profile_enable(False)
-    if serial_too:
-        S.set_overlap(s2_cus)
-        mode["pipe"] = True
-    ap = S.profile_query("s1_apply")
-    fa = S.profile_query("s1_factor")
-    sw = S.profile_query("s2_sweep")
-    bu = S.profile_query("s1_blkupd")
-    rp = S.profile_query("s1_rpass")
-    cq = S.profile_query("s1_cqr")
-    pp = S.profile_query("s1_prep")
-    cm = S.profile_query("s1_comm")   # the distributed blocked path's data movement around its collectives
-    blocked = bu["launches"] > 0
+    if args.full:
+        if serial_too:
+            # (2) the same kind of steps without any overlap (one reduction at a
+            # time, whole chip per stage): the latency of one reduction, reported
+            # beside the stream's throughput
+            mode["pipe"] = False
+            S.set_overlap(0)
+            el_s, s1_s, s2_s = run_steps(args.warmup + args.steps)
+            one_at_a_time = {"value": round(args.steps * 8.0 / 3.0 * n ** 3 / el_s / 1e9, 2),
+                             "ms_per_step": round(el_s / args.steps * 1e3, 3),
+                             "stage_ms": {"stage1": round(s1_s, 3), "stage2": round(s2_s, 3)}}
+        # (3) K steps with the library's per-launch HIP events on its launch
+        # streams: kernel durations for the roofline object.  On one GPU they run
+        # one reduction at a time (as in (2)), so a kernel's duration is its own,
+        # not stretched by the concurrent lanes of (1); across GPUs they repeat (1).
+        S.profile_reset()
+        S.profile_enable(True)
+        el_prof, _, _ = run_steps(args.warmup + (2 if serial_too else 1) * args.steps)
+        S.profile_enable(False)
+        if serial_too:
+            S.set_overlap(s2_cus)
+            mode["pipe"] = True
+        ap = S.profile_query("s1_apply")
+        fa = S.profile_query("s1_factor")
+        sw = S.profile_query("s2_sweep")
+        bu = S.profile_query("s1_blkupd")
+        rp = S.profile_query("s1_rpass")
+        cq = S.profile_query("s1_cqr")
+        pp = S.profile_query("s1_prep")
+        cm = S.profile_query("s1_comm")   # the distributed blocked path's data movement around its collectives
+        blocked = bu["launches"] > 0
 
     flops_per = 8.0 / 3.0 * n ** 3
     matrices = 1 if (world == 1 or dist_mode) else world   # matrices reduced per step, whole job
@@ -701,7 +753,7 @@ def main():
     # so the line carries a like-for-like 1 -> N efficiency at this size
     same_n = None
     rehearse = os.environ.get("BRD_BENCH_SAME_N") == "1"   # world-1 rehearsal (--force-dist)
-    if (world > 1 or rehearse) and dist_mode and args.comm == "rccl" and args.same_n == "on":
+    if args.full and (world > 1 or rehearse) and dist_mode and args.comm == "rccl" and args.same_n == "on":
         if rank == 0:
             try:
                 same_n = single_gpu_same_n(S, torch, dev, n, b, tdt, args.steps, max(1, args.warmup), lanes,
@@ -737,7 +789,7 @@ def main():
                                        f"stream(s) (matrix j's stage 2 on stream j mod {s2_lanes}, after its stage 1, "
                                        "beside the following matrices' stage 1), fill and drain inside the timed region; "
                                        "per-reduction latency under overlap: latency_ms_per_reduction; one reduction "
-                                       "at a time: one_at_a_time") if pipelined else "one reduction at a time"),
+                                       "at a time: one_at_a_time (--full)") if pipelined else "one reduction at a time"),
                        "n": n, "band": b,
                        # matrices in flight at once: one per lane in the stream
                        "global_batch": matrices * (lanes if pipelined else 1),
@@ -751,34 +803,37 @@ def main():
                        "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),
                        "rccl_nranks": world if (dist_mode and args.comm == "rccl") else None},
             "latency_ms_per_reduction": round(s1 + s2, 3),
-            # host time to issue the K steps' launches: the timed pass (, one at a time, profiled)
+            # host time to issue the K steps' launches: the timed pass (--full: , one at a time, profiled)
             "host_issue_ms": [round(x, 1) for x in host_issue_ms],
-            "one_at_a_time": one_at_a_time,
             "stage_ms": {"stage1": round(s1, 3), "stage2": round(s2, 3)},
-            "profiled_ms_per_step": round(el_prof / args.steps * 1e3, 3),
-            "profiled_pass": "one reduction at a time" if serial_too else "as the timed steps",
-            # the dominant stage-1 kernel: the blocked path's delayed update
-            # (k_blkupd, MFMA-bound) when it ran, else the per-panel apply
-            "roofline": blkupd_roofline(bu, args.dtype, n) if blocked else apply_roofline(ap, args.dtype, n),
-            "roofline_read_pass": rpass_roofline(rp, args.dtype, n) if blocked else None,
-            "roofline_tail_apply": apply_roofline(ap, args.dtype, n) if blocked and ap["launches"] else None,
-            "stage2": stage2_roofline(sw, n, b, args.dtype, args.steps),
-            "kernel_ms_per_step": {"s1_blkupd": round(bu["ms"] / args.steps, 3),
-                                   "s1_rpass": round(rp["ms"] / args.steps, 3),
-                                   "s1_panel_cqr": round(cq["ms"] / args.steps, 3),
-                                   "s1_prep": round(pp["ms"] / args.steps, 3),
-                                   "s1_comm": round(cm["ms"] / args.steps, 3),
-                                   "s1_apply": round(ap["ms"] / args.steps, 3),
-                                   "s1_factor": round(fa["ms"] / args.steps, 3),
-                                   "s2_sweep": round(sw["ms"] / args.steps, 3)},
-            "stage1_path": "blocked (delayed two-sided update, brd_stage1_blk.hip) + per-panel tail" if blocked
-                           else "per-panel (brd_stage1.hip)",
         }
+        if args.full:
+            out.update({
+                "one_at_a_time": one_at_a_time,
+                "profiled_ms_per_step": round(el_prof / args.steps * 1e3, 3),
+                "profiled_pass": "one reduction at a time" if serial_too else "as the timed steps",
+                # the dominant stage-1 kernel: the blocked path's delayed update
+                # (k_blkupd, MFMA-bound) when it ran, else the per-panel apply
+                "roofline": blkupd_roofline(bu, args.dtype, n) if blocked else apply_roofline(ap, args.dtype, n),
+                "roofline_read_pass": rpass_roofline(rp, args.dtype, n) if blocked else None,
+                "roofline_tail_apply": apply_roofline(ap, args.dtype, n) if blocked and ap["launches"] else None,
+                "stage2": stage2_roofline(sw, n, b, args.dtype, args.steps),
+                "kernel_ms_per_step": {"s1_blkupd": round(bu["ms"] / args.steps, 3),
+                                       "s1_rpass": round(rp["ms"] / args.steps, 3),
+                                       "s1_panel_cqr": round(cq["ms"] / args.steps, 3),
+                                       "s1_prep": round(pp["ms"] / args.steps, 3),
+                                       "s1_comm": round(cm["ms"] / args.steps, 3),
+                                       "s1_apply": round(ap["ms"] / args.steps, 3),
+                                       "s1_factor": round(fa["ms"] / args.steps, 3),
+                                       "s2_sweep": round(sw["ms"] / args.steps, 3)},
+                "stage1_path": "blocked (delayed two-sided update, brd_stage1_blk.hip) + per-panel tail" if blocked
+                               else "per-panel (brd_stage1.hip)",
+            })
         if same_n is not None:
             out["single_gpu_same_n"] = same_n
             out["efficiency_vs_single_gpu_same_n"] = (round(value / (world * same_n["value"]), 4)
                                                       if same_n.get("value") else None)
-        if args.cpu_baseline == "auto":
+        if args.full and args.cpu_baseline == "auto":
             try:
                 out["cpu_baseline"] = cpu_baseline([int(x) for x in args.cpu_n.split(",")], b, n)
             except Exception as e:   # the baseline is reported, never required

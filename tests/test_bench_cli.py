@@ -61,7 +61,7 @@ def test_bench_two_ranks_end_to_end():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", f"--master-port={_free_port()}", os.path.join(REPO, "bench.py"),
            "--gpus", "2", "--comm", "host", "--size", "1024", "--steps", "3", "--warmup", "1",
-           "--lanes", "2", "--cpu-baseline", "off"]
+           "--lanes", "2", "--cpu-baseline", "off", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=REPO)
@@ -83,7 +83,7 @@ def test_bench_eight_ranks_end_to_end():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=8",
            "--master-addr", "127.0.0.1", f"--master-port={_free_port()}", os.path.join(REPO, "bench.py"),
            "--gpus", "8", "--comm", "host", "--size", "2048", "--steps", "2", "--warmup", "1",
-           "--lanes", "2", "--cpu-baseline", "off"]
+           "--lanes", "2", "--cpu-baseline", "off", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=400, env=env, cwd=REPO)
@@ -93,3 +93,44 @@ def test_bench_eight_ranks_end_to_end():
     d = json.loads(lines[0])
     assert d["n_gpus"] == 8 and d["value"] > 0 and d["config"]["n"] == 2048
     assert d["config"]["matrices_per_timed_region"] == 2
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain one-GPU run: the line holds the headline figure and none of the
+    --full measurements, and --dump-outputs writes the last timed step's
+    matrix (every step reduces a copy of the same seeded input): its diagonal
+    and superdiagonal are the bidiagonal that the same two library calls
+    compute here from that input.  The bound is smoke()'s for the fast stage 2
+    (1e-8 in the relative 2-norm of |d|, |e|: the stream's launches are sized
+    for a shared chip, so the order of its sums may differ)."""
+    import json
+    import numpy as np
+    import torch
+    import svdsolver_amd as S
+    n, b, steps = 512, 32, 3
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--size", str(n),
+                          "--steps", str(steps), "--warmup", "1", "--dump-outputs", str(tmp_path / "o")],
+                         capture_output=True, text=True, timeout=240, cwd=REPO)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == steps and line["config"]["matrices_per_timed_region"] == steps
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["dtype"] == "f64"
+    assert line["value"] == pytest.approx(8.0 / 3.0 * n ** 3 / (line["ms_per_step"] * 1e-3) / 1e9, rel=1e-2)
+    for key in ("one_at_a_time", "roofline", "kernel_ms_per_step", "cpu_baseline"):
+        assert key not in line
+    d, e, full = (np.load(tmp_path / "o" / f"{name}.npy") for name in ("d", "e", "matrix"))
+    assert d.dtype == e.dtype == full.dtype == np.float64
+    assert d.shape == (n,) and e.shape == (n - 1,) and full.shape == (n, n)
+    assert np.array_equal(np.diagonal(full), d) and np.array_equal(np.diagonal(full, 1), e)
+    g = torch.Generator(device="cuda:0")
+    g.manual_seed(1234)
+    A = torch.rand((n, n), dtype=torch.float64, device="cuda:0", generator=g) * 5.0
+    S.ge2band(A, b)
+    d_ref, e_ref = (x.cpu().numpy() for x in S.band2bd(A, b))
+    for got, ref in ((d, d_ref), (e, e_ref)):
+        err = np.linalg.norm(np.abs(got) - np.abs(ref)) / np.linalg.norm(ref)
+        print(f"dumped bidiagonal vs in-process: {err:.2e}")
+        assert err < 1e-8

@@ -6,7 +6,7 @@
 # steps:
 #   tests            all -m gpu tests (pytest, per-test timeouts)
 #   smoke            __graft_entry__.smoke()
-#   bench[:ARGS]     one bench.py line (ARGS: comma-separated extra flags, e.g. bench:--dtype,f32)
+#   bench[:ARGS]     one bench.py --full line (ARGS: comma-separated extra flags, e.g. bench:--dtype,f32)
 #   prof[:N:DT:ARGS] rocprofv3 --kernel-trace --stats of a short bench (default one reduction at a time)
 #   pmc[:N:DT:ARGS]  FETCH_SIZE / WRITE_SIZE passes (tools/pmc.sh) at N, dtype DT (+ bench args)
 #   s1[:N]           stage-1 timing (tools/s1time.py)
@@ -29,7 +29,8 @@ for st in "$@"; do
         || { echo SMOKE FAILED; tail -5 gpurun_out/s_$tag.log; exit 1; }
       tail -1 gpurun_out/s_$tag.log ;;
     bench)
-      a=${arg//,/ }; k=$(echo "$a" | tr -cd 'a-z0-9' | cut -c1-24)
+      # --full: the line read below holds the one-at-a-time, per-kernel and roofline figures
+      k=$(echo "$arg" | tr -cd 'a-z0-9' | cut -c1-24); a="--full ${arg//,/ }"
       timeout -k 10 600 python bench.py $a > gpurun_out/b_${tag}_$k.log 2>&1 \
         || { echo BENCH FAILED; tail -5 gpurun_out/b_${tag}_$k.log; exit 1; }
       grep metric gpurun_out/b_${tag}_$k.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('BENCH', d['value'], d['ms_per_step'], d['stage_ms'], d.get('one_at_a_time'), d['kernel_ms_per_step'], d['roofline']['frac'])" ;;

@@ -1,7 +1,7 @@
 """CU occupancy of a stream of reductions from the library's own launch
 timeline (developer tool; rocprofv3's kernel trace serialises the lanes).
 Record it with BRD_PROF_TRACE=<file> around a profiled pass, e.g.
-    BRD_PROF_TRACE=gpurun_out/tl.txt python bench.py --one-at-a-time off
+    BRD_PROF_TRACE=tl.txt python bench.py --full --one-at-a-time off
 (the profiled pass then repeats the stream with per-launch events).
 Every stage-1 / stage-2 workgroup holds a whole CU (LDS), so a launch's CU
 time is min(workgroups, CUs) x duration; stage 2 (grid unknown here) counts

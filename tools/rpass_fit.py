@@ -1,5 +1,5 @@
 """Read-pass launches of a one-at-a-time run from the library's launch
-timeline (BRD_PROF_TRACE, bench.py --pipeline off): duration against the
+timeline (BRD_PROF_TRACE, bench.py --full --pipeline off): duration against the
 algorithmic bytes, a least-squares t = t0 + bytes / BW fit over the passes
 (the fixed cost per pass and the streaming rate), and the time split by
 pass size.  usage: python tools/rpass_fit.py <trace> [kind=s1_rpass]"""
