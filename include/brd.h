@@ -82,6 +82,21 @@ int brd_bdsvd_f32(const float *d, const float *e, int n, float *sv);
 int brd_bdsvd_dev_f64(const double *d, const double *e, int n, double *sv, unsigned flags);
 int brd_bdsvd_dev_f32(const float *d, const float *e, int n, float *sv, unsigned flags);
 
+/* SVD of `batch` small m x n matrices (n <= m; n <= 64, m <= 128), one launch:
+ * A_i = U_i diag(S_i) V_i^T by one-sided Jacobi.  All pointers are DEVICE
+ * pointers; matrices are row-major: A_i = A + i*stride_a, element (r,c) at
+ * [r*lda + c].  S: batch x n, descending, S_i = S + i*n.  U (m x n per matrix)
+ * and V (n x n per matrix: V, not V^T) may both be NULL: values only.
+ * info: batch ints, required (0 converged, 1 sweep cap, 2 non-finite input).
+ * A is not modified.  Runs on the library stream; BRD_ASYNC returns without
+ * waiting.  Sizes beyond the limits: BRD_EUNSUPPORTED. */
+int brd_svd_batched_f64(const double *A, int batch, int m, int n, int lda, long stride_a,
+                        double *S, double *U, int ldu, long stride_u,
+                        double *V, int ldv, long stride_v, int *info, unsigned flags);
+int brd_svd_batched_f32(const float *A, int batch, int m, int n, int lda, long stride_a,
+                        float *S, float *U, int ldu, long stride_u,
+                        float *V, int ldv, long stride_v, int *info, unsigned flags);
+
 /* Stream used by subsequent calls (hipStream_t; NULL = the legacy default
  * stream).  Until the first call the library uses a stream of its own;
  * brd_use_own_stream() reverts to it. */
@@ -116,7 +131,9 @@ int brd_release_stream(void *hip_stream);
 
 /* Per-kernel device timing for roofline reporting.  While enabled, the library
  * brackets every launch of the named kernel class with HIP events on the
- * launch stream.  kernel: "s1_apply", "s1_factor", "s2_sweep".  Returns the
+ * launch stream.  kernel: "s1_apply", "s1_factor", "s2_sweep", "svd_batched"
+ * (credited with the bytes of A read and of S, U, V, info written; no flops:
+ * the sweep count depends on the data).  Returns the
  * number of launches, their total device time in ms and the algorithmic flops
  * and bytes those launches were credited with. */
 int brd_profile_enable(int enable);

@@ -41,6 +41,7 @@ EXPORTED = (
     "brd_dist_unique_id", "brd_dist_init", "brd_dist_init_host", "brd_dist_finalize", "brd_dist_local_cols",
     "brd_ge2band_dist_f64", "brd_ge2band_dist_f32", "brd_dist_gather_band_f64", "brd_dist_gather_band_f32",
     "brd_bdsvd_f64", "brd_bdsvd_f32", "brd_bdsvd_dev_f64", "brd_bdsvd_dev_f32", "brd_last_error", "brd_version",
+    "brd_svd_batched_f64", "brd_svd_batched_f32",
 )
 
 # brd_coll_fn (include/brd.h): int (*)(int op, const void *send, void *recv,
@@ -86,6 +87,9 @@ def _load() -> ctypes.CDLL:
         hd = getattr(L, f"brd_bdsvd_dev_{t}")
         hd.argtypes = [vp, vp, ci, vp, cu]
         hd.restype = ci
+        sb = getattr(L, f"brd_svd_batched_{t}")
+        sb.argtypes = [vp, ci, ci, ci, ci, ctypes.c_long, vp, vp, ci, ctypes.c_long, vp, ci, ctypes.c_long, vp, cu]
+        sb.restype = ci
     L.brd_set_stream.argtypes = [vp]
     L.brd_set_stream.restype = ci
     L.brd_use_own_stream.argtypes = []
@@ -301,6 +305,78 @@ def singular_values(A, b: int = 32):
     B = brd_p1(A, b)
     _, d, e = brd_p2(B, b, sigma=True)
     return bdsvd(d, e)
+
+
+# ---------------------------------------------------------------------------
+# batched SVD of small matrices (one-sided Jacobi, one launch)
+# ---------------------------------------------------------------------------
+def svd_batched(A, *, compute_uv: bool = True, check: bool = True, sync: bool = True):
+    """SVD of a batch of small matrices in one kernel launch (brd_svd_batched_*,
+    one-sided Jacobi; every matrix at most 128 x 64 or 64 x 128).  ``A`` is a
+    float32/float64 torch CUDA tensor ``(batch, m, n)`` or ``(m, n)`` with
+    contiguous rows (any row and batch stride); it is not modified.
+
+    Returns ``(U, S, Vh)`` shaped like ``torch.linalg.svd(A,
+    full_matrices=False)`` (``Vh`` is the transposed view of the library's V),
+    or ``S`` alone when ``compute_uv`` is False.  Singular values are
+    descending and relatively accurate for column-scaled matrices.
+
+    ``check`` (implies a synchronise and one small copy): raise
+    :class:`BrdError` naming the matrices that hit the sweep cap (info 1);
+    matrices with a NaN or Inf (info 2) keep their all-NaN outputs, as torch
+    does.  With ``check=False`` the per-matrix ``info`` tensor (int32) is
+    returned as an extra last element and nothing is raised."""
+    import torch
+    if not _is_torch_cuda(A):
+        raise ValueError("svd_batched takes a torch CUDA tensor")
+    if A.dim() not in (2, 3):
+        raise ValueError("A must be (batch, m, n) or (m, n)")
+    sfx = _sfx(A.dtype)
+    single = A.dim() == 2
+    A3 = A.unsqueeze(0) if single else A
+    batch, m, n = A3.shape
+    if batch < 1 or m < 1 or n < 1:
+        raise ValueError("svd_batched needs batch, m, n >= 1")
+    wide = m < n
+    if wide:   # the C ABI keeps m >= n: decompose A^T = V S U^T
+        A3 = A3.transpose(1, 2).contiguous()
+        m, n = n, m
+    if A3.stride(2) != 1 or A3.stride(1) < n or (batch > 1 and A3.stride(0) < (m - 1) * A3.stride(1) + n):
+        raise ValueError("A must have unit column stride, row stride >= n and non-overlapping matrices")
+    lda = int(A3.stride(1))
+    stride_a = int(A3.stride(0)) if batch > 1 else m * lda
+    S = torch.empty((batch, n), dtype=A.dtype, device=A.device)
+    info = torch.empty(batch, dtype=torch.int32, device=A.device)
+    U = V = None
+    if compute_uv:
+        U = torch.empty((batch, m, n), dtype=A.dtype, device=A.device)
+        V = torch.empty((batch, n, n), dtype=A.dtype, device=A.device)
+    _bind_stream(A)
+    fn = f"brd_svd_batched_{sfx}"
+    wait = sync or check
+    _check(fn, getattr(lib, fn)(ctypes.c_void_p(A3.data_ptr()), batch, m, n, lda, stride_a,
+                                ctypes.c_void_p(S.data_ptr()),
+                                ctypes.c_void_p(U.data_ptr() if compute_uv else 0), n, m * n,
+                                ctypes.c_void_p(V.data_ptr() if compute_uv else 0), n, n * n,
+                                ctypes.c_void_p(info.data_ptr()), 0 if wait else BRD_ASYNC))
+    if check:
+        capped = torch.nonzero(info == 1).flatten().tolist()
+        if capped:
+            raise BrdError(fn, 1, f"sweep cap reached for matrices {capped}")
+    if single:
+        S, info = S[0], info[0]
+        if compute_uv:
+            U, V = U[0], V[0]
+    if not compute_uv:
+        return S if check else (S, info)
+    # A = U S V^T; a wide input was decomposed as A^T = U S V^T, so A = V S U^T
+    out = (V, S, U.transpose(-2, -1)) if wide else (U, S, V.transpose(-2, -1))
+    return out if check else out + (info,)
+
+
+def svdvals_batched(A, **kw):
+    """Singular values only: ``svd_batched(A, compute_uv=False, **kw)``."""
+    return svd_batched(A, compute_uv=False, **kw)
 
 
 # ---------------------------------------------------------------------------

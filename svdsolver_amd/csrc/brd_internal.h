@@ -115,6 +115,13 @@ hipError_t launch_extract_bidiag(const T *A, int n, long lda, T *d, T *e, hipStr
 template <typename T>
 hipError_t launch_bdsvd_dev(const T *d, const T *e, int n, T *sv, T *ws, hipStream_t s);
 
+// Batched SVD of small matrices by one-sided Jacobi (brd_svd_batched.hip): one
+// launch, device pointers, n <= m, n <= 64, m <= 128 (else
+// hipErrorInvalidValue).  U and V both null: values only.
+template <typename T>
+hipError_t launch_svd_batched(const T *A, int batch, int m, int n, long lda, long stride_a, T *S, T *U, long ldu,
+                              long stride_u, T *V, long ldv, long stride_v, int *info, hipStream_t s);
+
 // ---- services of the C-ABI layer (brd_api.cpp) used by the distributed
 // driver (brd_dist.hip) ------------------------------------------------------
 int api_fail(int code, const char *msg);           // sets brd_last_error, returns code

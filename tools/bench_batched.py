@@ -1,0 +1,99 @@
+"""Timing of the batched small-matrix SVD (svd_batched) on the GPU, in one run:
+
+  (a) svd_batched, values only and with vectors;
+  (b) the route the library offered before it: a loop of
+      singular_values_gpu(A_i, b=min(32, n)) over 64 of the same matrices, per
+      matrix (square shapes only);
+  (c) torch.linalg.svdvals / torch.linalg.svd on the whole batch.
+
+fp64 and fp32 at batch x m x n = 16384x16x16, 4096x32x32, 2048x64x64 and
+1024x128x64, uniform(0, 5) entries from a fixed seed.  Every shape is warmed
+up first; each figure is the median of five windows of at least 0.3 s between
+device events, with the spread (max - min) of the five.  The sweeps come from
+the numpy model of the kernel's method (tests/jacobi_model.py) on the first
+two matrices of each batch.
+
+    python tools/bench_batched.py [--out profiles/batched_svd.json] [--skip-torch]
+"""
+import argparse
+import json
+import math
+import os
+import sys
+
+import numpy as np
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.join(REPO, "tests"))
+import svdsolver_amd as S  # noqa: E402
+from jacobi_model import jacobi_svd  # noqa: E402
+
+SHAPES = [(16384, 16, 16), (4096, 32, 32), (2048, 64, 64), (1024, 128, 64)]
+WINDOW_S, REPEATS, LOOP_MATRICES = 0.3, 5, 64
+
+
+def window_ms(fn, reps):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def measure(fn):
+    """Median and spread (ms per call) of REPEATS windows of >= WINDOW_S."""
+    fn()   # warm-up
+    torch.cuda.synchronize()
+    once = max(window_ms(fn, 1), 1e-3)
+    reps = max(1, math.ceil(WINDOW_S * 1e3 / once))
+    ts = [window_ms(fn, reps) for _ in range(REPEATS)]
+    return {"median_ms": float(np.median(ts)), "spread_ms": float(max(ts) - min(ts)), "calls_per_window": reps}
+
+
+def per_matrix(r, count):
+    return {"median_us": r["median_ms"] * 1e3 / count, "spread_us": r["spread_ms"] * 1e3 / count,
+            "calls_per_window": r["calls_per_window"]}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "batched_svd.json"))
+    ap.add_argument("--skip-torch", action="store_true", help="leave out measurement (c)")
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    props = torch.cuda.get_device_properties(dev)
+    result = {"device": props.name, "cus": props.multi_processor_count, "window_s": WINDOW_S, "repeats": REPEATS,
+              "unit": "microseconds per matrix", "rows": []}
+    for dt in (torch.float64, torch.float32):
+        for batch, m, n in SHAPES:
+            g = torch.Generator(device=dev).manual_seed(1234)
+            A = torch.rand((batch, m, n), dtype=dt, device=dev, generator=g) * 5
+            row = {"dtype": str(dt).replace("torch.", ""), "batch": batch, "m": m, "n": n}
+            npdt = np.float64 if dt == torch.float64 else np.float32
+            row["model_sweeps"] = [int(jacobi_svd(A[i].cpu().numpy(), dtype=npdt)[4]) for i in range(2)]
+            info = S.svd_batched(A, check=False)[3]
+            row["info_nonzero"] = int((info != 0).sum())
+            row["svd_batched_values"] = per_matrix(measure(lambda: S.svdvals_batched(A, check=False, sync=False)), batch)
+            row["svd_batched_vectors"] = per_matrix(measure(lambda: S.svd_batched(A, check=False, sync=False)), batch)
+            if m == n:
+                def loop():
+                    for i in range(LOOP_MATRICES):
+                        S.singular_values_gpu(A[i], b=min(32, n))
+                row["loop_singular_values_gpu"] = per_matrix(measure(loop), LOOP_MATRICES)
+            if not args.skip_torch:
+                row["torch_svdvals"] = per_matrix(measure(lambda: torch.linalg.svdvals(A)), batch)
+                row["torch_svd"] = per_matrix(measure(lambda: torch.linalg.svd(A, full_matrices=False)), batch)
+            result["rows"].append(row)
+            print(json.dumps(row), flush=True)
+            os.makedirs(os.path.dirname(args.out), exist_ok=True)
+            with open(args.out, "w") as f:   # rewritten after every shape: a cut-short run keeps its rows
+                json.dump(result, f, indent=1)
+                f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
