@@ -97,6 +97,31 @@ int brd_svd_batched_f32(const float *A, int batch, int m, int n, int lda, long s
                         float *S, float *U, int ldu, long stride_u,
                         float *V, int ldv, long stride_v, int *info, unsigned flags);
 
+/* Batched SVD of tall matrices: any m >= n with 1 <= n <= 64 (n > 64:
+ * BRD_EUNSUPPORTED).  Householder QR of every matrix in row blocks (A = Q R,
+ * A read once), brd_svd_batched's Jacobi kernel on the n x n factors R, then
+ * U = Q U_R: three launches on the library stream with no host
+ * synchronisation between them.  Arguments, layout, outputs, info and flags
+ * are exactly those of brd_svd_batched_*; column scaling keeps the relative
+ * accuracy (QR does not mix columns).  m <= 128 forwards to brd_svd_batched_*
+ * (bitwise its result; needs no workspace).
+ * work: device memory of at least brd_svd_tall_batched_work_bytes(batch, m, n,
+ * vectors, elem_bytes) bytes (vectors: 1 when U and V are given, else 0;
+ * elem_bytes: 8 or 4), owned by the caller and free again when the call's
+ * work on the stream is done; it holds R and, with vectors, U_R and one
+ * Householder scalar per column per row block.  The query returns a negative
+ * brd_status for sizes the call rejects and 0 when nothing is needed (work
+ * may then be NULL); work_bytes too small: BRD_EINVAL. */
+long brd_svd_tall_batched_work_bytes(int batch, int m, int n, int vectors, int elem_bytes);
+int brd_svd_tall_batched_f64(const double *A, int batch, int m, int n, int lda, long stride_a,
+                             double *S, double *U, int ldu, long stride_u,
+                             double *V, int ldv, long stride_v, int *info,
+                             void *work, long work_bytes, unsigned flags);
+int brd_svd_tall_batched_f32(const float *A, int batch, int m, int n, int lda, long stride_a,
+                             float *S, float *U, int ldu, long stride_u,
+                             float *V, int ldv, long stride_v, int *info,
+                             void *work, long work_bytes, unsigned flags);
+
 /* Stream used by subsequent calls (hipStream_t; NULL = the legacy default
  * stream).  Until the first call the library uses a stream of its own;
  * brd_use_own_stream() reverts to it. */
@@ -133,7 +158,10 @@ int brd_release_stream(void *hip_stream);
  * brackets every launch of the named kernel class with HIP events on the
  * launch stream.  kernel: "s1_apply", "s1_factor", "s2_sweep", "svd_batched"
  * (credited with the bytes of A read and of S, U, V, info written; no flops:
- * the sweep count depends on the data).  Returns the
+ * the sweep count depends on the data), "svd_tall_batched" (one entry per
+ * call spanning its three launches, credited like "svd_batched"; the stages
+ * of a call beyond 128 rows also under "svd_tall_qr", "svd_tall_jacobi" and
+ * "svd_tall_apply", time only).  Returns the
  * number of launches, their total device time in ms and the algorithmic flops
  * and bytes those launches were credited with. */
 int brd_profile_enable(int enable);

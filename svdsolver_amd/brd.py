@@ -42,6 +42,7 @@ EXPORTED = (
     "brd_ge2band_dist_f64", "brd_ge2band_dist_f32", "brd_dist_gather_band_f64", "brd_dist_gather_band_f32",
     "brd_bdsvd_f64", "brd_bdsvd_f32", "brd_bdsvd_dev_f64", "brd_bdsvd_dev_f32", "brd_last_error", "brd_version",
     "brd_svd_batched_f64", "brd_svd_batched_f32",
+    "brd_svd_tall_batched_work_bytes", "brd_svd_tall_batched_f64", "brd_svd_tall_batched_f32",
 )
 
 # brd_coll_fn (include/brd.h): int (*)(int op, const void *send, void *recv,
@@ -90,6 +91,11 @@ def _load() -> ctypes.CDLL:
         sb = getattr(L, f"brd_svd_batched_{t}")
         sb.argtypes = [vp, ci, ci, ci, ci, ctypes.c_long, vp, vp, ci, ctypes.c_long, vp, ci, ctypes.c_long, vp, cu]
         sb.restype = ci
+        st = getattr(L, f"brd_svd_tall_batched_{t}")
+        st.argtypes = sb.argtypes[:-1] + [vp, ctypes.c_long, cu]
+        st.restype = ci
+    L.brd_svd_tall_batched_work_bytes.argtypes = [ci, ci, ci, ci, ci]
+    L.brd_svd_tall_batched_work_bytes.restype = ctypes.c_long
     L.brd_set_stream.argtypes = [vp]
     L.brd_set_stream.restype = ci
     L.brd_use_own_stream.argtypes = []
@@ -326,9 +332,14 @@ def svd_batched(A, *, compute_uv: bool = True, check: bool = True, sync: bool = 
     matrices with a NaN or Inf (info 2) keep their all-NaN outputs, as torch
     does.  With ``check=False`` the per-matrix ``info`` tensor (int32) is
     returned as an extra last element and nothing is raised."""
+    return _svd_batched_call(A, "svd_batched", False, compute_uv, check, sync)
+
+
+def _svd_batched_call(A, name, tall, compute_uv, check, sync):
+    """svd_batched / svd_tall_batched: argument rules, outputs and the call."""
     import torch
     if not _is_torch_cuda(A):
-        raise ValueError("svd_batched takes a torch CUDA tensor")
+        raise ValueError(f"{name} takes a torch CUDA tensor")
     if A.dim() not in (2, 3):
         raise ValueError("A must be (batch, m, n) or (m, n)")
     sfx = _sfx(A.dtype)
@@ -336,7 +347,7 @@ def svd_batched(A, *, compute_uv: bool = True, check: bool = True, sync: bool = 
     A3 = A.unsqueeze(0) if single else A
     batch, m, n = A3.shape
     if batch < 1 or m < 1 or n < 1:
-        raise ValueError("svd_batched needs batch, m, n >= 1")
+        raise ValueError(f"{name} needs batch, m, n >= 1")
     wide = m < n
     if wide:   # the C ABI keeps m >= n: decompose A^T = V S U^T
         A3 = A3.transpose(1, 2).contiguous()
@@ -351,14 +362,22 @@ def svd_batched(A, *, compute_uv: bool = True, check: bool = True, sync: bool = 
     if compute_uv:
         U = torch.empty((batch, m, n), dtype=A.dtype, device=A.device)
         V = torch.empty((batch, n, n), dtype=A.dtype, device=A.device)
+    work = ()
+    if tall:   # the caller-owned workspace of the C ABI: a tensor that lives until the call has run
+        need = int(lib.brd_svd_tall_batched_work_bytes(batch, m, n, int(compute_uv), A.element_size()))
+        if need < 0:
+            raise BrdError("brd_svd_tall_batched_work_bytes", need, f"{m} x {n} matrices are not supported "
+                           "(at most 64 columns, or 64 rows for wide input)")
+        wbuf = torch.empty(max(need, 1), dtype=torch.uint8, device=A.device)
+        work = (ctypes.c_void_p(wbuf.data_ptr() if need else 0), need)
     _bind_stream(A)
-    fn = f"brd_svd_batched_{sfx}"
+    fn = f"brd_{name}_{sfx}"
     wait = sync or check
     _check(fn, getattr(lib, fn)(ctypes.c_void_p(A3.data_ptr()), batch, m, n, lda, stride_a,
                                 ctypes.c_void_p(S.data_ptr()),
                                 ctypes.c_void_p(U.data_ptr() if compute_uv else 0), n, m * n,
                                 ctypes.c_void_p(V.data_ptr() if compute_uv else 0), n, n * n,
-                                ctypes.c_void_p(info.data_ptr()), 0 if wait else BRD_ASYNC))
+                                ctypes.c_void_p(info.data_ptr()), *work, 0 if wait else BRD_ASYNC))
     if check:
         capped = torch.nonzero(info == 1).flatten().tolist()
         if capped:
@@ -377,6 +396,25 @@ def svd_batched(A, *, compute_uv: bool = True, check: bool = True, sync: bool = 
 def svdvals_batched(A, **kw):
     """Singular values only: ``svd_batched(A, compute_uv=False, **kw)``."""
     return svd_batched(A, compute_uv=False, **kw)
+
+
+def svd_tall_batched(A, *, compute_uv: bool = True, check: bool = True, sync: bool = True):
+    """SVD of a batch of tall matrices (brd_svd_tall_batched_*): any number of
+    rows, at most 64 columns (or the transpose of that).  Blocked Householder
+    QR of every matrix, :func:`svd_batched`'s Jacobi kernel on the n x n
+    factors, then U = Q U_R -- three launches, no host synchronisation between
+    them; relative accuracy for column-scaled matrices is kept.  Matrices of at
+    most 128 rows go to :func:`svd_batched`'s kernel unchanged.
+
+    Arguments, return values, ``check`` and ``sync`` are those of
+    :func:`svd_batched`.  The workspace the C ABI asks for is allocated here as
+    a torch tensor of the queried size."""
+    return _svd_batched_call(A, "svd_tall_batched", True, compute_uv, check, sync)
+
+
+def svdvals_tall_batched(A, **kw):
+    """Singular values only: ``svd_tall_batched(A, compute_uv=False, **kw)``."""
+    return svd_tall_batched(A, compute_uv=False, **kw)
 
 
 # ---------------------------------------------------------------------------

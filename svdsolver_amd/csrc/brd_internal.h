@@ -122,6 +122,20 @@ template <typename T>
 hipError_t launch_svd_batched(const T *A, int batch, int m, int n, long lda, long stride_a, T *S, T *U, long ldu,
                               long stride_u, T *V, long ldv, long stride_v, int *info, hipStream_t s);
 
+// Batched QR of tall matrices in row blocks and its back-application
+// (brd_qr_batched.hip), the front end of the batched tall SVD.  Factor: R
+// (batch x n x n, contiguous) and, when U and tau are given, the reflectors in
+// U and tau (batch x blocks x n, blocks = ceil(m / qr_tall_row_block(n))).
+// Apply: U = Q [U_R; 0] in place over the reflectors; matrices with info 2 get
+// NaN.  n <= 64, m >= n, else hipErrorInvalidValue.
+int qr_tall_row_block(int n);
+template <typename T>
+hipError_t launch_qr_tall_factor(const T *A, int batch, int m, int n, long lda, long stride_a, T *R, T *U, long ldu,
+                                 long stride_u, T *tau, hipStream_t s);
+template <typename T>
+hipError_t launch_qr_tall_apply(const T *UR, const T *tau, const int *info, int batch, int m, int n, T *U, long ldu,
+                                long stride_u, hipStream_t s);
+
 // ---- services of the C-ABI layer (brd_api.cpp) used by the distributed
 // driver (brd_dist.hip) ------------------------------------------------------
 int api_fail(int code, const char *msg);           // sets brd_last_error, returns code

@@ -14,6 +14,15 @@ the numpy model of the kernel's method (tests/jacobi_model.py) on the first
 two matrices of each batch.
 
     python tools/bench_batched.py [--out profiles/batched_svd.json] [--skip-torch]
+
+--tall times the batched tall SVD (svd_tall_batched) instead, by the same
+method, at batch x m x n = 4096x256x16, 1024x1024x32, 256x4096x64 and
+1024x512x64 (default output profiles/batched_svd_tall.json): values and
+vectors, torch.linalg.svdvals / svd on the same batch (on its first 128
+matrices, recorded as torch_batch, when one call on the whole batch takes more
+than a second), the share of the device time in the three stages (QR, Jacobi
+on R, back-application; from the library's profile classes over ten calls)
+and the values path's HBM rate against A read once.
 """
 import argparse
 import json
@@ -31,7 +40,9 @@ import svdsolver_amd as S  # noqa: E402
 from jacobi_model import jacobi_svd  # noqa: E402
 
 SHAPES = [(16384, 16, 16), (4096, 32, 32), (2048, 64, 64), (1024, 128, 64)]
+TALL_SHAPES = [(4096, 256, 16), (1024, 1024, 32), (256, 4096, 64), (1024, 512, 64)]
 WINDOW_S, REPEATS, LOOP_MATRICES = 0.3, 5, 64
+TORCH_SUBSET, TORCH_CALL_S, STAGE_CALLS = 128, 1.0, 10
 
 
 def window_ms(fn, reps):
@@ -59,15 +70,67 @@ def per_matrix(r, count):
             "calls_per_window": r["calls_per_window"]}
 
 
+def stage_shares(fn):
+    """Share of the device time of STAGE_CALLS calls in the three stages."""
+    torch.cuda.synchronize()
+    S.profile_enable(True)
+    S.profile_reset()
+    for _ in range(STAGE_CALLS):
+        fn()
+    torch.cuda.synchronize()
+    ms = {k: S.profile_query(f"svd_tall_{k}")["ms"] for k in ("qr", "jacobi", "apply")}
+    whole = S.profile_query("svd_tall_batched")["ms"]
+    S.profile_enable(False)
+    out = {k: v / whole for k, v in ms.items()}
+    out["call_us"] = whole * 1e3 / STAGE_CALLS
+    return out
+
+
+def tall_rows(args, dev, result):
+    for dt in (torch.float64, torch.float32):
+        for batch, m, n in TALL_SHAPES:
+            g = torch.Generator(device=dev).manual_seed(1234)
+            A = torch.rand((batch, m, n), dtype=dt, device=dev, generator=g) * 5
+            row = {"dtype": str(dt).replace("torch.", ""), "batch": batch, "m": m, "n": n}
+            info = S.svd_tall_batched(A, check=False)[3]
+            row["info_nonzero"] = int((info != 0).sum())
+            vals = measure(lambda: S.svdvals_tall_batched(A, check=False, sync=False))
+            row["svd_tall_batched_values"] = per_matrix(vals, batch)
+            row["svd_tall_batched_vectors"] = per_matrix(
+                measure(lambda: S.svd_tall_batched(A, check=False, sync=False)), batch)
+            row["values_hbm_tb_per_s"] = batch * m * n * A.element_size() / (vals["median_ms"] * 1e-3) / 1e12
+            row["stage_share_values"] = stage_shares(lambda: S.svdvals_tall_batched(A, check=False, sync=False))
+            row["stage_share_vectors"] = stage_shares(lambda: S.svd_tall_batched(A, check=False, sync=False))
+            if not args.skip_torch:
+                torch.linalg.svdvals(A[:2])   # library start-up is not the batch's time
+                torch.cuda.synchronize()
+                At = A if window_ms(lambda: torch.linalg.svdvals(A), 1) <= TORCH_CALL_S * 1e3 else A[:TORCH_SUBSET]
+                row["torch_batch"] = At.shape[0]
+                row["torch_svdvals"] = per_matrix(measure(lambda: torch.linalg.svdvals(At)), At.shape[0])
+                row["torch_svd"] = per_matrix(measure(lambda: torch.linalg.svd(At, full_matrices=False)), At.shape[0])
+            result["rows"].append(row)
+            print(json.dumps(row), flush=True)
+            os.makedirs(os.path.dirname(args.out), exist_ok=True)
+            with open(args.out, "w") as f:   # rewritten after every shape: a cut-short run keeps its rows
+                json.dump(result, f, indent=1)
+                f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "batched_svd.json"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--skip-torch", action="store_true", help="leave out measurement (c)")
+    ap.add_argument("--tall", action="store_true", help="the tall shapes through svd_tall_batched")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(REPO, "profiles", "batched_svd_tall.json" if args.tall else "batched_svd.json")
     dev = torch.device("cuda:0")
     props = torch.cuda.get_device_properties(dev)
     result = {"device": props.name, "cus": props.multi_processor_count, "window_s": WINDOW_S, "repeats": REPEATS,
               "unit": "microseconds per matrix", "rows": []}
+    if args.tall:
+        tall_rows(args, dev, result)
+        return
     for dt in (torch.float64, torch.float32):
         for batch, m, n in SHAPES:
             g = torch.Generator(device=dev).manual_seed(1234)
