@@ -5,6 +5,7 @@
 // form).  See brd_stage1_blk.hip for the algorithm.
 #pragma once
 
+#include "brd_blk_plan.h"
 #include "brd_internal.h"
 
 #include <hip/hip_ext.h>
@@ -46,7 +47,6 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 constexpr int NBMAX = 4;    // panels per block (Lw / RwT hold 2 NBMAX 32 = 256 vectors)
 constexpr int kRT = 512;    // threads: 4 column waves x 2 halves of the workgroup's K range
 constexpr int kWM = 64;     // m per wave
-constexpr int kMT = 256;    // m per workgroup
 #ifndef BRD_BLK_KSU
 #define BRD_BLK_KSU 8       // A/B knob (tools/variant_lib.sh)
 #endif
@@ -65,7 +65,8 @@ struct RpArgs {
     void *part; long mp;            // partials [ks][32][mp] (Y) / [ks][mp][32] (X)
     void *vpart;                    // virtual partials [ks][32][256] / [ks][256][32]
     void *vout;                     // virtual result [32][256] / [256][32]
-    int *counter;                   // (unused)
+    int *counter;                   // vfold: the virtual tile's arrival counter (k_rpass_d's atomic
+                                    // fetch-add; the last contributor sums, then resets it)
     int *err;
     int has_fin;                    // 1: workgroup 0 runs cqr_finish of the panel the pass follows
     int vfold = 0;                  // k_rpass_d: the virtual tile's partials summed in the pass (the
@@ -77,10 +78,6 @@ struct RpArgs {
 
 // ---- k_prep_* (brd_blk_prep.hip) ---------------------------------------------
 constexpr int kPT = 256;
-constexpr int kPI = 32;    // items per workgroup when split: two item waves x two halves of
-                           // the K1 range (the correction's MFMA chain over all four SIMDs;
-                           // the halves meet in LDS, fixed order); unsplit: 2 kPI items,
-                           // four item waves (when the split grid would exceed the CUs)
 
 constexpr int kGramRec = 1040;   // doubles per prep Gram record (1024 + exponent, 128-B lines of its own)
 struct PrepArgs {
@@ -160,18 +157,20 @@ struct CqrArgs {
 
 // scratch (doubles): three slots of Gram partials [kCW][1024] (two used), the
 // per-workgroup exponents, R1, the shifted-pass flag, and Q1 [32][kCW kCT]
-__host__ __device__ constexpr size_t cqr_ws_doubles() {   // gp3: the distributed middle pass
-    return (size_t)3 * 1024 * kCW + kCW + 2048 + 4 + (size_t)kCW * kCT * 32;
-}
+// (one definition of the offsets, host and device: the drivers use CqrWs too)
+__host__ __device__ constexpr size_t cqr_ws_gp(int slot) { return (size_t)slot * 1024 * kCW; }   // gp3: the distributed middle pass
+__host__ __device__ constexpr size_t cqr_ws_ew() { return cqr_ws_gp(3); }
+__host__ __device__ constexpr size_t cqr_ws_r1() { return cqr_ws_ew() + kCW; }
 // Q_t (qt) and the zero flag are read by the next read pass's finishing
 // workgroup (cqr_finish)
-__host__ __device__ constexpr size_t cqr_ws_qt() { return (size_t)3 * 1024 * kCW + kCW + 1024; }
+__host__ __device__ constexpr size_t cqr_ws_qt() { return cqr_ws_r1() + 1024; }
 __host__ __device__ constexpr size_t cqr_ws_zero() { return cqr_ws_qt() + 1024 + 2; }
+__host__ __device__ constexpr size_t cqr_ws_doubles() { return cqr_ws_zero() + 2 + (size_t)kCW * kCT * 32; }
 struct CqrWs {
     double *gp1, *gp2, *gp3, *ew, *r1, *qt, *shifted, *zero, *q1;
-    __device__ explicit CqrWs(double *ws)
-        : gp1(ws), gp2(ws + 1024 * kCW), gp3(ws + 2048 * kCW), ew(ws + 3072 * kCW), r1(ws + 3072 * kCW + kCW),
-          qt(ws + cqr_ws_qt()), shifted(ws + cqr_ws_qt() + 1024), zero(ws + cqr_ws_zero()),
+    __host__ __device__ explicit CqrWs(double *ws)
+        : gp1(ws + cqr_ws_gp(0)), gp2(ws + cqr_ws_gp(1)), gp3(ws + cqr_ws_gp(2)), ew(ws + cqr_ws_ew()),
+          r1(ws + cqr_ws_r1()), qt(ws + cqr_ws_qt()), shifted(ws + cqr_ws_qt() + 1024), zero(ws + cqr_ws_zero()),
           q1(ws + cqr_ws_zero() + 2) {}
 };
 
@@ -385,44 +384,10 @@ __device__ void cqr_finish_entry(const FinArgs &f, int tid, void *lds) {
 
 // ---- k_blkupd (brd_blk_upd.hip) ---------------------------------------------
 constexpr int kGT = 256;
-constexpr int kGM = 128;
 constexpr int kGKC = 16;
 constexpr int kGBP = kGM + 16;
 
-struct GemmArgs {
-    void *C; long ldc;
-    int rows, cols;                 // extent of the updated region
-    const void *Lw; const void *RwT; long ldr;
-    int K;                          // 256
-    int tiles_c;                    // column tiles
-    int ntiles;                     // tiles
-    int nfull = 0, nh = 0;          // k_blkupd_p: nh > 0: tiles [0, nfull) whole, then
-                                    // nh half tiles (64 rows) of tiles nfull, nfull + 1, ...
-    int xsr = 0, xsc = 0;           // k_blkupd_p: > 0: per-XCD super-tiles of xsr x xsc tiles
-                                    // (xsr xsc = grid / 8; blkupd_tile), else row-major order
-};
-
-// k_blkupd_p's tile order.  Tile q of the order -> (tile row, tile column).
-// With super-tiles (xsr > 0) the full xsr x xsc blocks come first, each one's
-// tiles row-major, then the right strip and the bottom strip row-major;
-// otherwise row-major.
-__host__ __device__ inline void blkupd_tile(const GemmArgs &a, int q, int &tr, int &tc) {
-    if (a.xsr <= 0) { tr = q / a.tiles_c; tc = q % a.tiles_c; return; }
-    const int tiles_r = a.ntiles / a.tiles_c, nsc = a.tiles_c / a.xsc;
-    const int Rf = (tiles_r / a.xsr) * a.xsr, Cf = nsc * a.xsc, per = a.xsr * a.xsc;
-    if (q < Rf * Cf) {
-        const int st = q / per, w = q - st * per;
-        tr = (st / nsc) * a.xsr + w / a.xsc;
-        tc = (st % nsc) * a.xsc + w % a.xsc;
-        return;
-    }
-    int e = q - Rf * Cf;
-    const int rw = a.tiles_c - Cf;
-    if (e < Rf * rw) { tr = e / rw; tc = Cf + e % rw; return; }
-    e -= Rf * rw;
-    tr = Rf + e / a.tiles_c;
-    tc = e % a.tiles_c;
-}
+// GemmArgs, blkupd_tile (k_blkupd_p's tile order): brd_blk_plan.h
 
 // ---- LDS-DMA and raw buffer accesses (k_blkupd_p, k_rpass_d) -----------------
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
@@ -482,24 +447,23 @@ static inline void blk_launch(const char *kind, double flops, double bytes, F ke
         hipLaunchKernelGGL(kernel, grid, block, 0, s, args...);
 }
 
-// host launchers, one per kernel family, defined beside the kernels
-// k_rpass_d (the LDS-DMA read pass) runs this pass: no 16-byte vector
-// straddling a source's end, rows 16-byte aligned, not disabled by
-// BRD_RPASS_DMA=0; its stages hold rpass_stage_k(elem) k each
+// host launchers, one per kernel family, defined beside the kernels; lc: the
+// call's launch plan (S1Launch) -- no launcher reads the environment or the
+// library's state.  rpass_dma_ok: k_rpass_d (the LDS-DMA read pass) can run
+// this pass: no 16-byte vector straddling a source's end, rows 16-byte aligned
 bool rpass_dma_ok(bool yp, int K, int M, size_t elem, const void *src, long ld, const void *vsrc, long vld,
                   const void *bsrc, long bld);
-int rpass_stage_k(size_t elem);
-template <typename T>
+template <typename T>   // a: filled from rpass_plan (wst > 0: k_rpass_d)
 void launch_k_rpass(bool yp, dim3 grid, const RpArgs &a, const FinArgs &f, hipStream_t s, double fl, double by);
 template <typename T>
 void launch_k_vsum(const T *vpart, T *vout, int nvirt, T *pbase, long pstride, const double *sgn, hipStream_t s);
-template <typename T>
-void launch_k_prep(bool lq, dim3 grid, const PrepArgs &p, hipStream_t s);
+template <typename T>   // split and the grid from prep_plan
+void launch_k_prep(bool lq, PrepArgs p, const S1Launch &lc, hipStream_t s);
 enum CqrKernel { kCqrGram, kCqrQ1, kCqrV, kCqrVInline, kCqrMid };
 template <typename T>
 void launch_k_cqr(CqrKernel which, int nwg, const CqrArgs &a, const FinArgs &f, hipStream_t s);
-template <typename T>
-void launch_k_blkupd(dim3 grid, const GemmArgs &g, hipStream_t s, double fl, double by);
+template <typename T>   // g: nfull, nh, xsr, xsc and the grid from blkupd_plan
+void launch_k_blkupd(GemmArgs g, const S1Launch &lc, hipStream_t s, double fl, double by);
 // the distributed path's data movement (brd_blk_comm.hip)
 template <typename T>
 void launch_dist_unpack_v(const T *src, T *dst, int M, hipStream_t s);

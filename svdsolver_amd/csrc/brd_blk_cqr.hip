@@ -855,8 +855,6 @@ __global__ void __launch_bounds__(kCT, 1) __attribute__((amdgpu_waves_per_eu(1, 
     }
 }
 
-
-
 template <typename T>
 void launch_k_cqr(CqrKernel which, int nwg, const CqrArgs &a, const FinArgs &f, hipStream_t s) {
     switch (which) {

@@ -625,12 +625,14 @@ __global__ void __launch_bounds__(kPT) k_prep_qr(PrepArgs a) {
 }
 
 template <typename T>
-void launch_k_prep(bool lq, dim3 grid, const PrepArgs &p, hipStream_t s) {
+void launch_k_prep(bool lq, PrepArgs p, const S1Launch &lc, hipStream_t s) {
     static_assert(NBMAX == 4, "the specialised panel indices below");
-    // BRD_PREP_GENERIC=1: the run-time-j forms only (read per launch: the
-    // parity test compares the two bit for bit)
-    const char *ge = getenv("BRD_PREP_GENERIC");
-    const int jsel = (ge && atoi(ge) != 0) ? -100 : p.j;
+    const PrepPlan pl = prep_plan(p.items, p.zfill, lc);
+    p.split = pl.split;
+    const dim3 grid(pl.grid);
+    // BRD_PREP_GENERIC=1: the run-time-j forms only (the parity test compares
+    // the two bit for bit)
+    const int jsel = lc.prep_generic ? -100 : p.j;
     if (lq) {
         switch (jsel) {
         case 0: blk_launch("s1_prep", 0.0, 0.0, k_prep_lq<T, 0>, grid, dim3(kPT), s, p); return;
@@ -650,8 +652,8 @@ void launch_k_prep(bool lq, dim3 grid, const PrepArgs &p, hipStream_t s) {
     default: blk_launch("s1_prep", 0.0, 0.0, k_prep_qr<T, -1, -1>, grid, dim3(kPT), s, p); return;
     }
 }
-template void launch_k_prep<double>(bool, dim3, const PrepArgs &, hipStream_t);
-template void launch_k_prep<float>(bool, dim3, const PrepArgs &, hipStream_t);
+template void launch_k_prep<double>(bool, PrepArgs, const S1Launch &, hipStream_t);
+template void launch_k_prep<float>(bool, PrepArgs, const S1Launch &, hipStream_t);
 
 }  // namespace blk
 }  // namespace brd

@@ -489,20 +489,14 @@ __global__ void __launch_bounds__(kRT, 1) k_rpass_d(RpArgs a, FinArgs fin) {
     }
 }
 
-static bool rpass_dma_enabled() {   // read per launch: parity tests switch it between calls
-    const char *e = getenv("BRD_RPASS_DMA");   // A/B: 0 = the register-streaming k_rpass
-    return !e || atoi(e) != 0;
-}
-
 bool rpass_dma_ok(bool yp, int K, int M, size_t elem, const void *src, long ld, const void *vsrc, long vld,
                   const void *bsrc, long bld) {
     // 16-byte vectors: no vector may straddle a source's end (Y tiles M wide,
     // X rows K long) and every row must start 16-byte aligned
     const long epv = 16 / (long)elem;
     auto al = [&](const void *p, long l) { return p == nullptr || ((uintptr_t)p % 16 == 0 && l % epv == 0); };
-    return rpass_dma_enabled() && (yp ? M % epv == 0 : K % epv == 0) && al(src, ld) && al(vsrc, vld) && al(bsrc, bld);
+    return (yp ? M % epv == 0 : K % epv == 0) && al(src, ld) && al(vsrc, vld) && al(bsrc, bld);
 }
-int rpass_stage_k(size_t elem) { return 128 / (int)elem; }
 
 template <typename T>
 void launch_k_rpass(bool yp, dim3 grid, const RpArgs &a, const FinArgs &f, hipStream_t s, double fl, double by) {

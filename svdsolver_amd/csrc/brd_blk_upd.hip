@@ -462,58 +462,21 @@ __global__ void __launch_bounds__(kGT2, 1) k_blkupd_p(GemmArgs a) {
     }
 }
 
-static int blkupd_persistent() {   // read per launch: parity tests switch it between calls
-    const char *e = getenv("BRD_BLKUPD_P");   // A/B: 0 = the two-per-CU kernel
-    return e ? atoi(e) : 1;
-}
-
 template <typename T>
-void launch_k_blkupd(dim3 grid, const GemmArgs &g, hipStream_t s, double fl, double by) {
-    {
-        // rows 16-byte aligned for the DMA granules (fp32: ldr, 256 and the
-        // bases multiples of 4 elements)
-        const bool al = sizeof(T) == 8 || (g.ldr % 4 == 0 && (uintptr_t)g.RwT % 16 == 0 && (uintptr_t)g.Lw % 16 == 0);
-        if (blkupd_persistent() && al) {
-            static int cus = 0;
-            if (!cus) {
-                int dev = 0;
-                hipGetDevice(&dev);
-                hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-            }
-            const int tgt = api_overlap_active() ? api_apply_target() : cus;
-            // The last round in half tiles when it leaves at least half the
-            // grid idle (r = ntiles mod tgt, 2 r <= tgt; bitwise the same
-            // band).  BRD_BLKUPD_HALF=0 turns it off (A/B).
-            GemmArgs gs = g;
-            const char *he = getenv("BRD_BLKUPD_HALF");
-            const int r = g.ntiles % tgt;
-            gs.nh = 0;
-            if ((he ? atoi(he) : 1) && r > 0 && 2 * r <= tgt) {
-                gs.nfull = g.ntiles - r;
-                gs.nh = 2 * r;
-            }
-            const int items = gs.nh > 0 ? gs.nfull + gs.nh : g.ntiles;
-            const int grid = std::min<int>(items, tgt);
-            if (gs.nh == 0) gs.nfull = g.ntiles;
-            // per-XCD super-tiles (blkupd_tile) when the grid deals whole rounds
-            // evenly over the 8 XCDs: 4 x (grid / 32) tiles, e.g. 4 x 8 on 256
-            // CUs, 4 x 7 beside a 32-CU stage-2 reservation.  BRD_BLKUPD_XCD=0 /
-            // 1 (A/B)
-            const char *xe = getenv("BRD_BLKUPD_XCD");
-            const int tiles_r = g.ntiles / g.tiles_c;
-            gs.xsr = gs.xsc = 0;
-            if ((xe ? atoi(xe) : 0) && grid % 32 == 0 && gs.nfull >= grid && tiles_r >= 4 && g.tiles_c >= grid / 32) {
-                gs.xsr = 4;
-                gs.xsc = grid / 32;
-            }
-            blk_launch("s1_blkupd", fl, by, k_blkupd_p<T>, dim3(grid), dim3(kGT2), s, gs);
-            return;
-        }
+void launch_k_blkupd(GemmArgs g, const S1Launch &lc, hipStream_t s, double fl, double by) {
+    // rows 16-byte aligned for the DMA granules (fp32: ldr, 256 and the bases
+    // multiples of 4 elements)
+    const bool al = sizeof(T) == 8 || (g.ldr % 4 == 0 && (uintptr_t)g.RwT % 16 == 0 && (uintptr_t)g.Lw % 16 == 0);
+    if (lc.blkupd_p && al) {
+        const UpdPlan u = blkupd_plan(g.ntiles, g.tiles_c, lc);
+        g.nfull = u.nfull; g.nh = u.nh; g.xsr = u.xsr; g.xsc = u.xsc;
+        blk_launch("s1_blkupd", fl, by, k_blkupd_p<T>, dim3(u.grid), dim3(kGT2), s, g);
+        return;
     }
-    blk_launch("s1_blkupd", fl, by, k_blkupd<T>, grid, dim3(kGT), s, g);   // BRD_BLKUPD_P=0 (A/B), unaligned fp32
+    blk_launch("s1_blkupd", fl, by, k_blkupd<T>, dim3(g.ntiles), dim3(kGT), s, g);   // BRD_BLKUPD_P=0 (A/B), unaligned fp32
 }
-template void launch_k_blkupd<double>(dim3, const GemmArgs &, hipStream_t, double, double);
-template void launch_k_blkupd<float>(dim3, const GemmArgs &, hipStream_t, double, double);
+template void launch_k_blkupd<double>(GemmArgs, const S1Launch &, hipStream_t, double, double);
+template void launch_k_blkupd<float>(GemmArgs, const S1Launch &, hipStream_t, double, double);
 
 }  // namespace blk
 }  // namespace brd
