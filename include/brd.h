@@ -97,6 +97,21 @@ int brd_svd_batched_f32(const float *A, int batch, int m, int n, int lda, long s
                         float *S, float *U, int ldu, long stride_u,
                         float *V, int ldv, long stride_v, int *info, unsigned flags);
 
+/* The same for mid-size matrices: 1 <= n <= m <= 128 (beyond 128 x 128:
+ * BRD_EUNSUPPORTED), one launch, one workgroup per matrix.  Arguments, layout,
+ * outputs, info, the NULL rules for U and V and flags are exactly those of
+ * brd_svd_batched_*; no workspace and no per-stream state, A is not modified.
+ * n <= 64 forwards to brd_svd_batched_* (bitwise its result).  For n > 64 in
+ * fp64 with vectors the kernel keeps its working copy of V in the caller's V
+ * block (only the n x n entries are ever touched), so V holds the result only
+ * when the call's work on the stream is done, like every other output. */
+int brd_svd_mid_batched_f64(const double *A, int batch, int m, int n, int lda, long stride_a,
+                            double *S, double *U, int ldu, long stride_u,
+                            double *V, int ldv, long stride_v, int *info, unsigned flags);
+int brd_svd_mid_batched_f32(const float *A, int batch, int m, int n, int lda, long stride_a,
+                            float *S, float *U, int ldu, long stride_u,
+                            float *V, int ldv, long stride_v, int *info, unsigned flags);
+
 /* Batched SVD of tall matrices: any m >= n with 1 <= n <= 64 (n > 64:
  * BRD_EUNSUPPORTED).  Householder QR of every matrix in row blocks (A = Q R,
  * A read once), brd_svd_batched's Jacobi kernel on the n x n factors R, then
@@ -158,7 +173,9 @@ int brd_release_stream(void *hip_stream);
  * brackets every launch of the named kernel class with HIP events on the
  * launch stream.  kernel: "s1_apply", "s1_factor", "s2_sweep", "svd_batched"
  * (credited with the bytes of A read and of S, U, V, info written; no flops:
- * the sweep count depends on the data), "svd_tall_batched" (one entry per
+ * the sweep count depends on the data), "svd_mid_batched" (one entry per
+ * brd_svd_mid_batched_* call, forwarded calls included, credited like
+ * "svd_batched"), "svd_tall_batched" (one entry per
  * call spanning its three launches, credited like "svd_batched"; the stages
  * of a call beyond 128 rows also under "svd_tall_qr", "svd_tall_jacobi" and
  * "svd_tall_apply", time only).  Returns the

@@ -41,7 +41,7 @@ EXPORTED = (
     "brd_dist_unique_id", "brd_dist_init", "brd_dist_init_host", "brd_dist_finalize", "brd_dist_local_cols",
     "brd_ge2band_dist_f64", "brd_ge2band_dist_f32", "brd_dist_gather_band_f64", "brd_dist_gather_band_f32",
     "brd_bdsvd_f64", "brd_bdsvd_f32", "brd_bdsvd_dev_f64", "brd_bdsvd_dev_f32", "brd_last_error", "brd_version",
-    "brd_svd_batched_f64", "brd_svd_batched_f32",
+    "brd_svd_batched_f64", "brd_svd_batched_f32", "brd_svd_mid_batched_f64", "brd_svd_mid_batched_f32",
     "brd_svd_tall_batched_work_bytes", "brd_svd_tall_batched_f64", "brd_svd_tall_batched_f32",
 )
 
@@ -91,7 +91,10 @@ def _load() -> ctypes.CDLL:
         sb = getattr(L, f"brd_svd_batched_{t}")
         sb.argtypes = [vp, ci, ci, ci, ci, ctypes.c_long, vp, vp, ci, ctypes.c_long, vp, ci, ctypes.c_long, vp, cu]
         sb.restype = ci
-        st = getattr(L, f"brd_svd_tall_batched_{t}")
+        sm = getattr(L, f"brd_svd_mid_batched_{t}")
+        sm.argtypes = list(sb.argtypes)
+        sm.restype = ci
+        st =getattr(L, f"brd_svd_tall_batched_{t}")
         st.argtypes = sb.argtypes[:-1] + [vp, ctypes.c_long, cu]
         st.restype = ci
     L.brd_svd_tall_batched_work_bytes.argtypes = [ci, ci, ci, ci, ci]
@@ -396,6 +399,23 @@ def _svd_batched_call(A, name, tall, compute_uv, check, sync):
 def svdvals_batched(A, **kw):
     """Singular values only: ``svd_batched(A, compute_uv=False, **kw)``."""
     return svd_batched(A, compute_uv=False, **kw)
+
+
+def svd_mid_batched(A, *, compute_uv: bool = True, check: bool = True, sync: bool = True):
+    """SVD of a batch of matrices of at most 128 x 128 in one kernel launch
+    (brd_svd_mid_batched_*, one-sided Jacobi, one workgroup per matrix).
+    Matrices with at most 64 columns (or rows, for wide input) go to
+    :func:`svd_batched`'s kernel unchanged; larger sizes raise
+    :class:`BrdError` (code -5).
+
+    Arguments, return values, ``check`` and ``sync`` are those of
+    :func:`svd_batched`."""
+    return _svd_batched_call(A, "svd_mid_batched", False, compute_uv, check, sync)
+
+
+def svdvals_mid_batched(A, **kw):
+    """Singular values only: ``svd_mid_batched(A, compute_uv=False, **kw)``."""
+    return svd_mid_batched(A, compute_uv=False, **kw)
 
 
 def svd_tall_batched(A, *, compute_uv: bool = True, check: bool = True, sync: bool = True):

@@ -720,6 +720,44 @@ static int svd_batched(const T *A, int batch, int m, int n, int lda, long stride
     return BRD_OK;
 }
 
+// Batched mid-size SVD (brd_svd_mid_batched.hip): n <= m <= 128 in one launch;
+// n <= 64 goes to the small kernel unchanged.  The checks and their order are
+// svd_batched's.
+template <typename T>
+static int svd_mid_batched(const T *A, int batch, int m, int n, int lda, long stride_a, T *S, T *U, int ldu,
+                           long stride_u, T *V, int ldv, long stride_v, int *info, unsigned flags) {
+    std::lock_guard<std::mutex> lk(g_ctx.mu);
+    if (!A || !S || !info) return fail(BRD_EINVAL, "brd_svd_mid_batched: A, S or info is NULL");
+    if (batch < 1) return fail(BRD_EINVAL, "brd_svd_mid_batched: need batch >= 1 (batch=%d)", batch);
+    if (n < 1) return fail(BRD_EINVAL, "brd_svd_mid_batched: need n >= 1 (n=%d)", n);
+    if (m < n) return fail(BRD_EINVAL, "brd_svd_mid_batched: need m >= n (m=%d n=%d)", m, n);
+    if (lda < n) return fail(BRD_EINVAL, "brd_svd_mid_batched: lda (%d) < n (%d)", lda, n);
+    if (stride_a < (long)(m - 1) * lda + n)
+        return fail(BRD_EINVAL, "brd_svd_mid_batched: stride_a (%ld) < (m-1) lda + n", stride_a);
+    if (U && (ldu < n || stride_u < (long)(m - 1) * ldu + n))
+        return fail(BRD_EINVAL, "brd_svd_mid_batched: ldu (%d) < n or stride_u (%ld) < (m-1) ldu + n", ldu, stride_u);
+    if (V && (ldv < n || stride_v < (long)(n - 1) * ldv + n))
+        return fail(BRD_EINVAL, "brd_svd_mid_batched: ldv (%d) < n or stride_v (%ld) < (n-1) ldv + n", ldv, stride_v);
+    if ((U == nullptr) != (V == nullptr))
+        return fail(BRD_EINVAL, "brd_svd_mid_batched: U and V must both be given or both be NULL");
+    if (m > 128)
+        return fail(BRD_EUNSUPPORTED, "brd_svd_mid_batched: %d x %d is beyond 128 x 128 (use the two-stage path)", m, n);
+    if (!is_device_ptr(A) || !is_device_ptr(S) || !is_device_ptr(info) || (U && (!is_device_ptr(U) || !is_device_ptr(V))))
+        return fail(BRD_EINVAL, "brd_svd_mid_batched: A, S, U, V and info must be device memory");
+    hipStream_t s = stream();
+    {
+        const double el = (double)batch * ((double)m * n + n + (U ? (double)m * n + (double)n * n : 0.0));
+        ProfScope ps("svd_mid_batched", 0, el * sizeof(T) + (double)batch * sizeof(int), s);
+        if (n <= 64) {
+            HIP_TRY(launch_svd_batched<T>(A, batch, m, n, lda, stride_a, S, U, ldu, stride_u, V, ldv, stride_v, info, s));
+        } else {
+            HIP_TRY(launch_svd_mid_batched<T>(A, batch, m, n, lda, stride_a, S, U, ldu, stride_u, V, ldv, stride_v, info, s));
+        }
+    }
+    if (!(flags & BRD_ASYNC)) HIP_TRY(hipStreamSynchronize(s));
+    return BRD_OK;
+}
+
 // Batched tall SVD (brd_qr_batched.hip around brd_svd_batched.hip): blocked
 // Householder QR, the Jacobi kernel on the R factors, U = Q U_R -- three
 // stream-ordered launches.  The workspace is the caller's: R, then (vectors)
@@ -829,6 +867,17 @@ int brd_svd_batched_f64(const double *A, int batch, int m, int n, int lda, long 
 int brd_svd_batched_f32(const float *A, int batch, int m, int n, int lda, long stride_a, float *S, float *U, int ldu,
                         long stride_u, float *V, int ldv, long stride_v, int *info, unsigned flags) {
     return brd::svd_batched<float>(A, batch, m, n, lda, stride_a, S, U, ldu, stride_u, V, ldv, stride_v, info, flags);
+}
+
+int brd_svd_mid_batched_f64(const double *A, int batch, int m, int n, int lda, long stride_a, double *S, double *U,
+                            int ldu, long stride_u, double *V, int ldv, long stride_v, int *info, unsigned flags) {
+    return brd::svd_mid_batched<double>(A, batch, m, n, lda, stride_a, S, U, ldu, stride_u, V, ldv, stride_v, info,
+                                        flags);
+}
+int brd_svd_mid_batched_f32(const float *A, int batch, int m, int n, int lda, long stride_a, float *S, float *U,
+                            int ldu, long stride_u, float *V, int ldv, long stride_v, int *info, unsigned flags) {
+    return brd::svd_mid_batched<float>(A, batch, m, n, lda, stride_a, S, U, ldu, stride_u, V, ldv, stride_v, info,
+                                       flags);
 }
 
 long brd_svd_tall_batched_work_bytes(int batch, int m, int n, int vectors, int elem_bytes) {

@@ -122,6 +122,13 @@ template <typename T>
 hipError_t launch_svd_batched(const T *A, int batch, int m, int n, long lda, long stride_a, T *S, T *U, long ldu,
                               long stride_u, T *V, long ldv, long stride_v, int *info, hipStream_t s);
 
+// The same for mid-size matrices (brd_svd_mid_batched.hip): one launch, one
+// workgroup per matrix, n <= m <= 128 (else hipErrorInvalidValue; meant for
+// n > 64).  fp64 with vectors keeps its working V in the caller's V block.
+template <typename T>
+hipError_t launch_svd_mid_batched(const T *A, int batch, int m, int n, long lda, long stride_a, T *S, T *U, long ldu,
+                                  long stride_u, T *V, long ldv, long stride_v, int *info, hipStream_t s);
+
 // Batched QR of tall matrices in row blocks and its back-application
 // (brd_qr_batched.hip), the front end of the batched tall SVD.  Factor: R
 // (batch x n x n, contiguous) and, when U and tau are given, the reflectors in

@@ -23,6 +23,14 @@ matrices, recorded as torch_batch, when one call on the whole batch takes more
 than a second), the share of the device time in the three stages (QR, Jacobi
 on R, back-application; from the library's profile classes over ten calls)
 and the values path's HBM rate against A read once.
+
+--mid times the batched mid-size SVD (svd_mid_batched, 65 to 128 columns)
+instead, by the same method, at batch x m x n = 1024x96x96, 1024x128x96 and
+1024x128x128 (default output profiles/batched_svd_mid.json): values and
+vectors and their ratio (in fp64 the vectors class keeps V in device memory),
+torch.linalg.svdvals / svd on the same batch (or its first 128 matrices, as
+above), the loop of singular_values_gpu(A_i, b=32) over 64 matrices at the
+square shapes, and the model's sweeps on the first two matrices.
 """
 import argparse
 import json
@@ -41,6 +49,7 @@ from jacobi_model import jacobi_svd  # noqa: E402
 
 SHAPES = [(16384, 16, 16), (4096, 32, 32), (2048, 64, 64), (1024, 128, 64)]
 TALL_SHAPES = [(4096, 256, 16), (1024, 1024, 32), (256, 4096, 64), (1024, 512, 64)]
+MID_SHAPES = [(1024, 96, 96), (1024, 128, 96), (1024, 128, 128)]
 WINDOW_S, REPEATS, LOOP_MATRICES = 0.3, 5, 64
 TORCH_SUBSET, TORCH_CALL_S, STAGE_CALLS = 128, 1.0, 10
 
@@ -116,20 +125,63 @@ def tall_rows(args, dev, result):
                 f.write("\n")
 
 
+def mid_rows(args, dev, result):
+    for dt in (torch.float64, torch.float32):
+        for batch, m, n in MID_SHAPES:
+            g = torch.Generator(device=dev).manual_seed(1234)
+            A = torch.rand((batch, m, n), dtype=dt, device=dev, generator=g) * 5
+            row = {"dtype": str(dt).replace("torch.", ""), "batch": batch, "m": m, "n": n}
+            npdt = np.float64 if dt == torch.float64 else np.float32
+            row["model_sweeps"] = [int(jacobi_svd(A[i].cpu().numpy(), dtype=npdt)[4]) for i in range(2)]
+            info = S.svd_mid_batched(A, check=False)[3]
+            row["info_nonzero"] = int((info != 0).sum())
+            vals = measure(lambda: S.svdvals_mid_batched(A, check=False, sync=False))
+            vecs = measure(lambda: S.svd_mid_batched(A, check=False, sync=False))
+            row["svd_mid_batched_values"] = per_matrix(vals, batch)
+            row["svd_mid_batched_vectors"] = per_matrix(vecs, batch)
+            row["vectors_over_values"] = vecs["median_ms"] / vals["median_ms"]
+            if m == n:
+                def loop():
+                    for i in range(LOOP_MATRICES):
+                        S.singular_values_gpu(A[i], b=32)
+                row["loop_singular_values_gpu"] = per_matrix(measure(loop), LOOP_MATRICES)
+            if not args.skip_torch:
+                torch.linalg.svdvals(A[:2])   # library start-up is not the batch's time
+                torch.cuda.synchronize()
+                At = A if window_ms(lambda: torch.linalg.svdvals(A), 1) <= TORCH_CALL_S * 1e3 else A[:TORCH_SUBSET]
+                row["torch_batch"] = At.shape[0]
+                row["torch_svdvals"] = per_matrix(measure(lambda: torch.linalg.svdvals(At)), At.shape[0])
+                row["torch_svd"] = per_matrix(measure(lambda: torch.linalg.svd(At, full_matrices=False)), At.shape[0])
+            result["rows"].append(row)
+            print(json.dumps(row), flush=True)
+            os.makedirs(os.path.dirname(args.out), exist_ok=True)
+            with open(args.out, "w") as f:   # rewritten after every shape: a cut-short run keeps its rows
+                json.dump(result, f, indent=1)
+                f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--skip-torch", action="store_true", help="leave out measurement (c)")
     ap.add_argument("--tall", action="store_true", help="the tall shapes through svd_tall_batched")
+    ap.add_argument("--mid", action="store_true", help="the 65..128-column shapes through svd_mid_batched")
     args = ap.parse_args()
+    if args.tall and args.mid:
+        ap.error("--tall and --mid are separate runs")
     if args.out is None:
-        args.out = os.path.join(REPO, "profiles", "batched_svd_tall.json" if args.tall else "batched_svd.json")
+        name = "batched_svd_tall.json" if args.tall else "batched_svd_mid.json" if args.mid else "batched_svd.json"
+        args.out = os.path.join(REPO, "profiles", name)
+    args.out = os.path.abspath(args.out)
     dev = torch.device("cuda:0")
     props = torch.cuda.get_device_properties(dev)
     result = {"device": props.name, "cus": props.multi_processor_count, "window_s": WINDOW_S, "repeats": REPEATS,
               "unit": "microseconds per matrix", "rows": []}
     if args.tall:
         tall_rows(args, dev, result)
+        return
+    if args.mid:
+        mid_rows(args, dev, result)
         return
     for dt in (torch.float64, torch.float32):
         for batch, m, n in SHAPES:
