@@ -137,6 +137,34 @@ int brd_svd_tall_batched_f32(const float *A, int batch, int m, int n, int lda, l
                              float *V, int ldv, long stride_v, int *info,
                              void *work, long work_bytes, unsigned flags);
 
+/* Batched SVD behind one entry point: any m >= n with 1 <= n <= 128 (n > 128:
+ * BRD_EUNSUPPORTED).  Arguments, layout, outputs, info, the NULL rule for U
+ * and V, flags, the argument checks and their order are those of
+ * brd_svd_tall_batched_*.  The call picks the route by size:
+ *   m <= 128, n <= 64: brd_svd_batched_*'s launch (bitwise its result);
+ *   m <= 128, n >  64: brd_svd_mid_batched_*'s launch (bitwise its result);
+ *   m >  128, n <= 64: brd_svd_tall_batched_*'s three launches (bitwise);
+ *   m >  128, n >  64: Householder QR in row blocks of 128 rows (A read once),
+ *     brd_svd_mid_batched's Jacobi kernel on the n x n factors R, U = Q U_R;
+ *     three launches with no host synchronisation between them.  In fp64 with
+ *     vectors the Jacobi step keeps its working V in the caller's V block, as
+ *     for brd_svd_mid_batched_*.
+ * work: as for brd_svd_tall_batched_*, of at least
+ * brd_gesvd_batched_work_bytes(batch, m, n, vectors, elem_bytes) bytes: 0 when
+ * m <= 128, brd_svd_tall_batched_work_bytes for n <= 64, and for n > 64
+ * batch * (n^2 + vectors * (n^2 + ceil(m / 128) * n)) * elem_bytes: R, U_R and
+ * one Householder scalar per column per row block.  On that last route R's
+ * upper triangle and U_R are also the kernels' working storage. */
+long brd_gesvd_batched_work_bytes(int batch, int m, int n, int vectors, int elem_bytes);
+int brd_gesvd_batched_f64(const double *A, int batch, int m, int n, int lda, long stride_a,
+                          double *S, double *U, int ldu, long stride_u,
+                          double *V, int ldv, long stride_v, int *info,
+                          void *work, long work_bytes, unsigned flags);
+int brd_gesvd_batched_f32(const float *A, int batch, int m, int n, int lda, long stride_a,
+                          float *S, float *U, int ldu, long stride_u,
+                          float *V, int ldv, long stride_v, int *info,
+                          void *work, long work_bytes, unsigned flags);
+
 /* Stream used by subsequent calls (hipStream_t; NULL = the legacy default
  * stream).  Until the first call the library uses a stream of its own;
  * brd_use_own_stream() reverts to it. */
@@ -178,6 +206,10 @@ int brd_release_stream(void *hip_stream);
  * "svd_batched"), "svd_tall_batched" (one entry per
  * call spanning its three launches, credited like "svd_batched"; the stages
  * of a call beyond 128 rows also under "svd_tall_qr", "svd_tall_jacobi" and
+ * "svd_tall_apply", time only), "gesvd_batched" (one entry per
+ * brd_gesvd_batched_* call on any route, credited like "svd_batched"; such a
+ * call records nothing under the three kinds before, and the stages of its
+ * two routes beyond 128 rows also under "svd_tall_qr", "svd_tall_jacobi" and
  * "svd_tall_apply", time only).  Returns the
  * number of launches, their total device time in ms and the algorithmic flops
  * and bytes those launches were credited with. */

@@ -43,6 +43,7 @@ EXPORTED = (
     "brd_bdsvd_f64", "brd_bdsvd_f32", "brd_bdsvd_dev_f64", "brd_bdsvd_dev_f32", "brd_last_error", "brd_version",
     "brd_svd_batched_f64", "brd_svd_batched_f32", "brd_svd_mid_batched_f64", "brd_svd_mid_batched_f32",
     "brd_svd_tall_batched_work_bytes", "brd_svd_tall_batched_f64", "brd_svd_tall_batched_f32",
+    "brd_gesvd_batched_work_bytes", "brd_gesvd_batched_f64", "brd_gesvd_batched_f32",
 )
 
 # brd_coll_fn (include/brd.h): int (*)(int op, const void *send, void *recv,
@@ -97,8 +98,12 @@ def _load() -> ctypes.CDLL:
         st =getattr(L, f"brd_svd_tall_batched_{t}")
         st.argtypes = sb.argtypes[:-1] + [vp, ctypes.c_long, cu]
         st.restype = ci
-    L.brd_svd_tall_batched_work_bytes.argtypes = [ci, ci, ci, ci, ci]
-    L.brd_svd_tall_batched_work_bytes.restype = ctypes.c_long
+        sg = getattr(L, f"brd_gesvd_batched_{t}")
+        sg.argtypes = list(st.argtypes)
+        sg.restype = ci
+    for q in (L.brd_svd_tall_batched_work_bytes, L.brd_gesvd_batched_work_bytes):
+        q.argtypes = [ci, ci, ci, ci, ci]
+        q.restype = ctypes.c_long
     L.brd_set_stream.argtypes = [vp]
     L.brd_set_stream.restype = ci
     L.brd_use_own_stream.argtypes = []
@@ -335,11 +340,13 @@ def svd_batched(A, *, compute_uv: bool = True, check: bool = True, sync: bool = 
     matrices with a NaN or Inf (info 2) keep their all-NaN outputs, as torch
     does.  With ``check=False`` the per-matrix ``info`` tensor (int32) is
     returned as an extra last element and nothing is raised."""
-    return _svd_batched_call(A, "svd_batched", False, compute_uv, check, sync)
+    return _svd_batched_call(A, "svd_batched", None, compute_uv, check, sync)
 
 
-def _svd_batched_call(A, name, tall, compute_uv, check, sync):
-    """svd_batched / svd_tall_batched: argument rules, outputs and the call."""
+def _svd_batched_call(A, name, work_query, compute_uv, check, sync):
+    """The batched SVD entry points: argument rules, outputs and the call.
+    ``work_query``: None, or (the name of the entry point's work-bytes query,
+    its column limit) when the C ABI takes a caller-owned workspace."""
     import torch
     if not _is_torch_cuda(A):
         raise ValueError(f"{name} takes a torch CUDA tensor")
@@ -366,11 +373,12 @@ def _svd_batched_call(A, name, tall, compute_uv, check, sync):
         U = torch.empty((batch, m, n), dtype=A.dtype, device=A.device)
         V = torch.empty((batch, n, n), dtype=A.dtype, device=A.device)
     work = ()
-    if tall:   # the caller-owned workspace of the C ABI: a tensor that lives until the call has run
-        need = int(lib.brd_svd_tall_batched_work_bytes(batch, m, n, int(compute_uv), A.element_size()))
+    if work_query:   # the caller-owned workspace of the C ABI: a tensor that lives until the call has run
+        query, limit = work_query
+        need = int(getattr(lib, query)(batch, m, n, int(compute_uv), A.element_size()))
         if need < 0:
-            raise BrdError("brd_svd_tall_batched_work_bytes", need, f"{m} x {n} matrices are not supported "
-                           "(at most 64 columns, or 64 rows for wide input)")
+            raise BrdError(query, need, f"{m} x {n} matrices are not supported "
+                           f"(at most {limit} columns, or {limit} rows for wide input)")
         wbuf = torch.empty(max(need, 1), dtype=torch.uint8, device=A.device)
         work = (ctypes.c_void_p(wbuf.data_ptr() if need else 0), need)
     _bind_stream(A)
@@ -410,7 +418,7 @@ def svd_mid_batched(A, *, compute_uv: bool = True, check: bool = True, sync: boo
 
     Arguments, return values, ``check`` and ``sync`` are those of
     :func:`svd_batched`."""
-    return _svd_batched_call(A, "svd_mid_batched", False, compute_uv, check, sync)
+    return _svd_batched_call(A, "svd_mid_batched", None, compute_uv, check, sync)
 
 
 def svdvals_mid_batched(A, **kw):
@@ -429,12 +437,32 @@ def svd_tall_batched(A, *, compute_uv: bool = True, check: bool = True, sync: bo
     Arguments, return values, ``check`` and ``sync`` are those of
     :func:`svd_batched`.  The workspace the C ABI asks for is allocated here as
     a torch tensor of the queried size."""
-    return _svd_batched_call(A, "svd_tall_batched", True, compute_uv, check, sync)
+    return _svd_batched_call(A, "svd_tall_batched", ("brd_svd_tall_batched_work_bytes", 64), compute_uv, check, sync)
 
 
 def svdvals_tall_batched(A, **kw):
     """Singular values only: ``svd_tall_batched(A, compute_uv=False, **kw)``."""
     return svd_tall_batched(A, compute_uv=False, **kw)
+
+
+def gesvd_batched(A, *, compute_uv: bool = True, check: bool = True, sync: bool = True):
+    """SVD of a batch of matrices of any number of rows and at most 128 columns
+    (or the transpose of that) behind one call (brd_gesvd_batched_*).  The
+    library picks the route by size: :func:`svd_batched`'s, :func:`svd_mid_batched`'s
+    or :func:`svd_tall_batched`'s kernels (bitwise their results), and beyond
+    128 rows with 65 to 128 columns a blocked Householder QR, the mid-size
+    Jacobi kernel on the n x n factors and U = Q U_R.  More than 128 rows and
+    columns raise :class:`BrdError` (code -5).
+
+    Arguments, return values, ``check`` and ``sync`` are those of
+    :func:`svd_batched`.  The workspace the C ABI asks for is allocated here as
+    a torch tensor of the queried size."""
+    return _svd_batched_call(A, "gesvd_batched", ("brd_gesvd_batched_work_bytes", 128), compute_uv, check, sync)
+
+
+def gesvdvals_batched(A, **kw):
+    """Singular values only: ``gesvd_batched(A, compute_uv=False, **kw)``."""
+    return gesvd_batched(A, compute_uv=False, **kw)
 
 
 # ---------------------------------------------------------------------------

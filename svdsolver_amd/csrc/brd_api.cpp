@@ -833,6 +833,101 @@ static int svd_tall_batched(const T *A, int batch, int m, int n, int lda, long s
     return BRD_OK;
 }
 
+// Batched SVD of any m >= n with n <= 128: one entry point over the four
+// routes (rows up to / beyond 128 x columns up to / beyond 64).  The first
+// three routes launch exactly what their own entry points launch; the fourth
+// is brd_qr_mid_batched.hip around brd_svd_mid_batched.hip.  The checks and
+// their order are svd_tall_batched's; the workspace is the caller's.
+static long gesvd_work_elems(int batch, int m, int n, int vectors) {
+    if (n <= 64) return tall_work_elems(batch, m, n, vectors);
+    if (m <= 128) return 0;   // forwarded to the mid-size Jacobi kernel as is
+    const long blocks = ((long)m + qr_tall_mid_row_block(n) - 1) / qr_tall_mid_row_block(n);
+    return (long)batch * ((long)n * n + (vectors ? (long)n * n + blocks * n : 0L));
+}
+
+static long gesvd_batched_work_bytes(int batch, int m, int n, int vectors, int elem_bytes) {
+    if (batch < 1 || n < 1 || m < n || (elem_bytes != 8 && elem_bytes != 4)) return BRD_EINVAL;
+    if (n > 128) return BRD_EUNSUPPORTED;
+    return gesvd_work_elems(batch, m, n, vectors) * elem_bytes;
+}
+
+template <typename T>
+static int gesvd_batched(const T *A, int batch, int m, int n, int lda, long stride_a, T *S, T *U, int ldu,
+                         long stride_u, T *V, int ldv, long stride_v, int *info, void *work, long work_bytes,
+                         unsigned flags) {
+    std::lock_guard<std::mutex> lk(g_ctx.mu);
+    if (!A || !S || !info) return fail(BRD_EINVAL, "brd_gesvd_batched: A, S or info is NULL");
+    if (batch < 1) return fail(BRD_EINVAL, "brd_gesvd_batched: need batch >= 1 (batch=%d)", batch);
+    if (n < 1) return fail(BRD_EINVAL, "brd_gesvd_batched: need n >= 1 (n=%d)", n);
+    if (m < n) return fail(BRD_EINVAL, "brd_gesvd_batched: need m >= n (m=%d n=%d)", m, n);
+    if (lda < n) return fail(BRD_EINVAL, "brd_gesvd_batched: lda (%d) < n (%d)", lda, n);
+    if (stride_a < (long)(m - 1) * lda + n)
+        return fail(BRD_EINVAL, "brd_gesvd_batched: stride_a (%ld) < (m-1) lda + n", stride_a);
+    if (U && (ldu < n || stride_u < (long)(m - 1) * ldu + n))
+        return fail(BRD_EINVAL, "brd_gesvd_batched: ldu (%d) < n or stride_u (%ld) < (m-1) ldu + n", ldu, stride_u);
+    if (V && (ldv < n || stride_v < (long)(n - 1) * ldv + n))
+        return fail(BRD_EINVAL, "brd_gesvd_batched: ldv (%d) < n or stride_v (%ld) < (n-1) ldv + n", ldv, stride_v);
+    if ((U == nullptr) != (V == nullptr))
+        return fail(BRD_EINVAL, "brd_gesvd_batched: U and V must both be given or both be NULL");
+    if (n > 128)
+        return fail(BRD_EUNSUPPORTED, "brd_gesvd_batched: n = %d is beyond 128 columns (use the two-stage path)", n);
+    const long need = gesvd_work_elems(batch, m, n, U != nullptr) * (long)sizeof(T);
+    if (need > 0 && (!work || work_bytes < need))
+        return fail(BRD_EINVAL, "brd_gesvd_batched: work is NULL or work_bytes (%ld) < %ld "
+                                "(brd_gesvd_batched_work_bytes)", work_bytes, need);
+    if (need > 0 && ((uintptr_t)work % sizeof(T)) != 0)
+        return fail(BRD_EINVAL, "brd_gesvd_batched: work is not aligned to the element size");
+    if (!is_device_ptr(A) || !is_device_ptr(S) || !is_device_ptr(info) || (U && (!is_device_ptr(U) || !is_device_ptr(V))) ||
+        (need > 0 && !is_device_ptr(work)))
+        return fail(BRD_EINVAL, "brd_gesvd_batched: A, S, U, V, info and work must be device memory");
+    hipStream_t s = stream();
+    {
+        const double el = (double)batch * ((double)m * n + n + (U ? (double)m * n + (double)n * n : 0.0));
+        ProfScope ps("gesvd_batched", 0, el * sizeof(T) + (double)batch * sizeof(int), s);
+        const bool mid = n > 64;
+        if (need == 0) {
+            if (mid) {
+                HIP_TRY(launch_svd_mid_batched<T>(A, batch, m, n, lda, stride_a, S, U, ldu, stride_u, V, ldv, stride_v, info, s));
+            } else {
+                HIP_TRY(launch_svd_batched<T>(A, batch, m, n, lda, stride_a, S, U, ldu, stride_u, V, ldv, stride_v, info, s));
+            }
+        } else {
+            const long nn = (long)n * n;
+            T *R = (T *)work;
+            T *UR = U ? R + batch * nn : nullptr;
+            T *tau = U ? UR + batch * nn : nullptr;
+            // the stages under the tall route's kinds (time only: the bytes are the call's)
+            {
+                ProfScope p1("svd_tall_qr", 0, 0, s);
+                if (mid) {
+                    HIP_TRY(launch_qr_tall_mid_factor<T>(A, batch, m, n, lda, stride_a, R, U, ldu, stride_u, tau, s));
+                } else {
+                    HIP_TRY(launch_qr_tall_factor<T>(A, batch, m, n, lda, stride_a, R, U, ldu, stride_u, tau, s));
+                }
+            }
+            {
+                // fp64 with vectors at n > 64: the Jacobi kernel keeps its working V in the caller's V block
+                ProfScope p2("svd_tall_jacobi", 0, 0, s);
+                if (mid) {
+                    HIP_TRY(launch_svd_mid_batched<T>(R, batch, n, n, n, nn, S, UR, n, nn, V, ldv, stride_v, info, s));
+                } else {
+                    HIP_TRY(launch_svd_batched<T>(R, batch, n, n, n, nn, S, UR, n, nn, V, ldv, stride_v, info, s));
+                }
+            }
+            if (U) {
+                ProfScope p3("svd_tall_apply", 0, 0, s);
+                if (mid) {
+                    HIP_TRY(launch_qr_tall_mid_apply<T>(UR, tau, info, batch, m, n, U, ldu, stride_u, s));
+                } else {
+                    HIP_TRY(launch_qr_tall_apply<T>(UR, tau, info, batch, m, n, U, ldu, stride_u, s));
+                }
+            }
+        }
+    }
+    if (!(flags & BRD_ASYNC)) HIP_TRY(hipStreamSynchronize(s));
+    return BRD_OK;
+}
+
 }  // namespace brd
 
 // ==========================================================================
@@ -894,6 +989,22 @@ int brd_svd_tall_batched_f32(const float *A, int batch, int m, int n, int lda, l
                              long work_bytes, unsigned flags) {
     return brd::svd_tall_batched<float>(A, batch, m, n, lda, stride_a, S, U, ldu, stride_u, V, ldv, stride_v, info,
                                         work, work_bytes, flags);
+}
+
+long brd_gesvd_batched_work_bytes(int batch, int m, int n, int vectors, int elem_bytes) {
+    return brd::gesvd_batched_work_bytes(batch, m, n, vectors, elem_bytes);
+}
+int brd_gesvd_batched_f64(const double *A, int batch, int m, int n, int lda, long stride_a, double *S, double *U,
+                          int ldu, long stride_u, double *V, int ldv, long stride_v, int *info, void *work,
+                          long work_bytes, unsigned flags) {
+    return brd::gesvd_batched<double>(A, batch, m, n, lda, stride_a, S, U, ldu, stride_u, V, ldv, stride_v, info, work,
+                                      work_bytes, flags);
+}
+int brd_gesvd_batched_f32(const float *A, int batch, int m, int n, int lda, long stride_a, float *S, float *U,
+                          int ldu, long stride_u, float *V, int ldv, long stride_v, int *info, void *work,
+                          long work_bytes, unsigned flags) {
+    return brd::gesvd_batched<float>(A, batch, m, n, lda, stride_a, S, U, ldu, stride_u, V, ldv, stride_v, info, work,
+                                     work_bytes, flags);
 }
 
 int brd_set_stream(void *hip_stream) {

@@ -143,6 +143,19 @@ template <typename T>
 hipError_t launch_qr_tall_apply(const T *UR, const T *tau, const int *info, int batch, int m, int n, T *U, long ldu,
                                 long stride_u, hipStream_t s);
 
+// The 128-column class of the same front end (brd_qr_mid_batched.hip; meant
+// for 65 <= n <= 128 and m > 128, the front end of the mid-size Jacobi
+// kernel): n <= 128, m >= n, else hipErrorInvalidValue.  R's strict upper
+// triangle lives in the workspace's R while the kernel runs, and the apply
+// kernel updates UR in place (it does not survive the call).
+int qr_tall_mid_row_block(int n);
+template <typename T>
+hipError_t launch_qr_tall_mid_factor(const T *A, int batch, int m, int n, long lda, long stride_a, T *R, T *U,
+                                     long ldu, long stride_u, T *tau, hipStream_t s);
+template <typename T>
+hipError_t launch_qr_tall_mid_apply(T *UR, const T *tau, const int *info, int batch, int m, int n, T *U, long ldu,
+                                    long stride_u, hipStream_t s);
+
 // ---- services of the C-ABI layer (brd_api.cpp) used by the distributed
 // driver (brd_dist.hip) ------------------------------------------------------
 int api_fail(int code, const char *msg);           // sets brd_last_error, returns code

@@ -31,6 +31,14 @@ vectors and their ratio (in fp64 the vectors class keeps V in device memory),
 torch.linalg.svdvals / svd on the same batch (or its first 128 matrices, as
 above), the loop of singular_values_gpu(A_i, b=32) over 64 matrices at the
 square shapes, and the model's sweeps on the first two matrices.
+
+--tall-mid times the batched tall mid-size SVD (gesvd_batched beyond 128 rows
+with 65 to 128 columns) instead, by the method of --tall, at batch x m x n =
+1024x512x96, 1024x512x128, 256x4096x128 and 1024x256x72 (default output
+profiles/batched_svd_tall_mid.json): values and vectors, the stage shares, the
+values path's HBM rate, torch as above, and the loop of singular_values_gpu
+over 64 of the matrices padded with zero columns to m x m (the only way the
+two-stage path takes them; shapes of at most 512 rows).
 """
 import argparse
 import json
@@ -50,6 +58,8 @@ from jacobi_model import jacobi_svd  # noqa: E402
 SHAPES = [(16384, 16, 16), (4096, 32, 32), (2048, 64, 64), (1024, 128, 64)]
 TALL_SHAPES = [(4096, 256, 16), (1024, 1024, 32), (256, 4096, 64), (1024, 512, 64)]
 MID_SHAPES = [(1024, 96, 96), (1024, 128, 96), (1024, 128, 128)]
+TALL_MID_SHAPES = [(1024, 512, 96), (1024, 512, 128), (256, 4096, 128), (1024, 256, 72)]
+LOOP_MAX_ROWS = 512   # the two-stage loop pads to m x m
 WINDOW_S, REPEATS, LOOP_MATRICES = 0.3, 5, 64
 TORCH_SUBSET, TORCH_CALL_S, STAGE_CALLS = 128, 1.0, 10
 
@@ -79,7 +89,7 @@ def per_matrix(r, count):
             "calls_per_window": r["calls_per_window"]}
 
 
-def stage_shares(fn):
+def stage_shares(fn, whole_kind="svd_tall_batched"):
     """Share of the device time of STAGE_CALLS calls in the three stages."""
     torch.cuda.synchronize()
     S.profile_enable(True)
@@ -88,7 +98,7 @@ def stage_shares(fn):
         fn()
     torch.cuda.synchronize()
     ms = {k: S.profile_query(f"svd_tall_{k}")["ms"] for k in ("qr", "jacobi", "apply")}
-    whole = S.profile_query("svd_tall_batched")["ms"]
+    whole = S.profile_query(whole_kind)["ms"]
     S.profile_enable(False)
     out = {k: v / whole for k, v in ms.items()}
     out["call_us"] = whole * 1e3 / STAGE_CALLS
@@ -117,6 +127,48 @@ def tall_rows(args, dev, result):
                 row["torch_batch"] = At.shape[0]
                 row["torch_svdvals"] = per_matrix(measure(lambda: torch.linalg.svdvals(At)), At.shape[0])
                 row["torch_svd"] = per_matrix(measure(lambda: torch.linalg.svd(At, full_matrices=False)), At.shape[0])
+            result["rows"].append(row)
+            print(json.dumps(row), flush=True)
+            os.makedirs(os.path.dirname(args.out), exist_ok=True)
+            with open(args.out, "w") as f:   # rewritten after every shape: a cut-short run keeps its rows
+                json.dump(result, f, indent=1)
+                f.write("\n")
+
+
+def tall_mid_rows(args, dev, result):
+    for dt in (torch.float64, torch.float32):
+        for batch, m, n in TALL_MID_SHAPES:
+            g = torch.Generator(device=dev).manual_seed(1234)
+            A = torch.rand((batch, m, n), dtype=dt, device=dev, generator=g) * 5
+            row = {"dtype": str(dt).replace("torch.", ""), "batch": batch, "m": m, "n": n}
+            info = S.gesvd_batched(A, check=False)[3]
+            row["info_nonzero"] = int((info != 0).sum())
+            vals = measure(lambda: S.gesvdvals_batched(A, check=False, sync=False))
+            row["gesvd_batched_values"] = per_matrix(vals, batch)
+            row["gesvd_batched_vectors"] = per_matrix(
+                measure(lambda: S.gesvd_batched(A, check=False, sync=False)), batch)
+            row["values_hbm_tb_per_s"] = batch * m * n * A.element_size() / (vals["median_ms"] * 1e-3) / 1e12
+            row["stage_share_values"] = stage_shares(lambda: S.gesvdvals_batched(A, check=False, sync=False),
+                                                     "gesvd_batched")
+            row["stage_share_vectors"] = stage_shares(lambda: S.gesvd_batched(A, check=False, sync=False),
+                                                      "gesvd_batched")
+            if m <= LOOP_MAX_ROWS:
+                P = torch.zeros((LOOP_MATRICES, m, m), dtype=dt, device=dev)
+                P[:, :, :n] = A[:LOOP_MATRICES]
+
+                def loop():
+                    for i in range(LOOP_MATRICES):
+                        S.singular_values_gpu(P[i], b=32)
+                row["loop_singular_values_gpu_padded"] = per_matrix(measure(loop), LOOP_MATRICES)
+            if not args.skip_torch:
+                torch.linalg.svdvals(A[:2])   # library start-up is not the batch's time
+                torch.cuda.synchronize()
+                At = A if window_ms(lambda: torch.linalg.svdvals(A), 1) <= TORCH_CALL_S * 1e3 else A[:TORCH_SUBSET]
+                row["torch_batch"] = At.shape[0]
+                row["torch_svdvals"] = per_matrix(measure(lambda: torch.linalg.svdvals(At)), At.shape[0])
+                row["torch_svd"] = per_matrix(measure(lambda: torch.linalg.svd(At, full_matrices=False)), At.shape[0])
+                row["torch_over_values"] = row["torch_svdvals"]["median_us"] / row["gesvd_batched_values"]["median_us"]
+                row["torch_over_vectors"] = row["torch_svd"]["median_us"] / row["gesvd_batched_vectors"]["median_us"]
             result["rows"].append(row)
             print(json.dumps(row), flush=True)
             os.makedirs(os.path.dirname(args.out), exist_ok=True)
@@ -166,11 +218,14 @@ def main():
     ap.add_argument("--skip-torch", action="store_true", help="leave out measurement (c)")
     ap.add_argument("--tall", action="store_true", help="the tall shapes through svd_tall_batched")
     ap.add_argument("--mid", action="store_true", help="the 65..128-column shapes through svd_mid_batched")
+    ap.add_argument("--tall-mid", action="store_true",
+                    help="more than 128 rows with 65..128 columns through gesvd_batched")
     args = ap.parse_args()
-    if args.tall and args.mid:
-        ap.error("--tall and --mid are separate runs")
+    if args.tall + args.mid + args.tall_mid > 1:
+        ap.error("--tall, --mid and --tall-mid are separate runs")
     if args.out is None:
-        name = "batched_svd_tall.json" if args.tall else "batched_svd_mid.json" if args.mid else "batched_svd.json"
+        name = ("batched_svd_tall.json" if args.tall else "batched_svd_mid.json" if args.mid else
+                "batched_svd_tall_mid.json" if args.tall_mid else "batched_svd.json")
         args.out = os.path.join(REPO, "profiles", name)
     args.out = os.path.abspath(args.out)
     dev = torch.device("cuda:0")
@@ -182,6 +237,9 @@ def main():
         return
     if args.mid:
         mid_rows(args, dev, result)
+        return
+    if args.tall_mid:
+        tall_mid_rows(args, dev, result)
         return
     for dt in (torch.float64, torch.float32):
         for batch, m, n in SHAPES:
