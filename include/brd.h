@@ -165,6 +165,47 @@ int brd_gesvd_batched_f32(const float *A, int batch, int m, int n, int lda, long
                           float *V, int ldv, long stride_v, int *info,
                           void *work, long work_bytes, unsigned flags);
 
+/* Batched least squares and pseudo-inverse through the batched SVD: for every
+ * matrix, the minimum-norm x minimising |A x - b|_2,
+ *     X = V diag(sigma+) U^T B,   sigma+_j = 1 / sigma_j where sigma_j > rcond sigma_1, else 0,
+ * from brd_gesvd_batched_*'s factors (its launches, then one more, on the
+ * library stream with no host synchronisation between them).  Shapes are those
+ * of brd_gesvd_batched_*: m >= n, 1 <= n <= 128 (n > 128: BRD_EUNSUPPORTED),
+ * any m; all pointers are DEVICE pointers, everything is row-major.
+ *   B: m x nrhs per matrix (element (r,c) of matrix i at B[i*stride_b + r*ldb + c]),
+ *   X: n x nrhs per matrix, likewise with ldx, stride_x.
+ * BRD_LS_TRANS solves A^T x = b instead (the minimum-norm solution; how wide
+ * problems are posed): B is then n x nrhs and X is m x nrhs.
+ * B == NULL stands for the identity and nrhs is ignored: X is n x m, the
+ * pseudo-inverse of A (with BRD_LS_TRANS m x n, the pseudo-inverse of A^T).
+ * rcond < 0 selects max(m, n) * eps of the type.  S (batch x n, the singular
+ * values, descending) and rank (batch ints: the number of values kept) may be
+ * NULL.  info: batch ints, required, as for brd_gesvd_batched_*; a matrix with
+ * info 2 (non-finite A) gets NaN in X and rank -1.  A and B are not modified;
+ * X must not overlap them.  BRD_ASYNC returns without waiting.
+ * work: device memory, 256-byte aligned, of at least
+ * brd_gelss_batched_work_bytes(batch, m, n, nrhs, elem_bytes) =
+ *   r(brd_gesvd_batched_work_bytes(batch, m, n, 1, elem_bytes))
+ *   + r(batch m n elem_bytes) + r(batch n n elem_bytes) + r(batch n elem_bytes)
+ * bytes with r(x) = x rounded up to a multiple of 256: brd_gesvd_batched's own
+ * workspace, U, V and S in this order (nrhs does not enter: the solve keeps
+ * its working tile on chip).  The query returns a negative brd_status for
+ * sizes the call rejects.
+ * Argument checks: those of brd_gesvd_batched_* first, in its order; then
+ * nrhs >= 1 (B given), ldb / stride_b, ldx / stride_x, X non-NULL, work. */
+#define BRD_LS_TRANS 0x20u   /* solve A^T x = b (minimum norm): B is n x nrhs, X is m x nrhs */
+long brd_gelss_batched_work_bytes(int batch, int m, int n, int nrhs, int elem_bytes);
+int brd_gelss_batched_f64(const double *A, int batch, int m, int n, int lda, long stride_a,
+                          const double *B, int nrhs, int ldb, long stride_b,
+                          double *X, int ldx, long stride_x,
+                          double rcond, double *S, int *rank, int *info,
+                          void *work, long work_bytes, unsigned flags);
+int brd_gelss_batched_f32(const float *A, int batch, int m, int n, int lda, long stride_a,
+                          const float *B, int nrhs, int ldb, long stride_b,
+                          float *X, int ldx, long stride_x,
+                          float rcond, float *S, int *rank, int *info,
+                          void *work, long work_bytes, unsigned flags);
+
 /* Stream used by subsequent calls (hipStream_t; NULL = the legacy default
  * stream).  Until the first call the library uses a stream of its own;
  * brd_use_own_stream() reverts to it. */
@@ -210,7 +251,12 @@ int brd_release_stream(void *hip_stream);
  * brd_gesvd_batched_* call on any route, credited like "svd_batched"; such a
  * call records nothing under the three kinds before, and the stages of its
  * two routes beyond 128 rows also under "svd_tall_qr", "svd_tall_jacobi" and
- * "svd_tall_apply", time only).  Returns the
+ * "svd_tall_apply", time only), "gelss_batched" (one entry per
+ * brd_gelss_batched_* call, credited with the bytes of A and B read and of X
+ * and S written; such a call records nothing under "gesvd_batched" or the
+ * kinds before it, its SVD stages beyond 128 rows under the three
+ * "svd_tall_*" kinds and its last launch under "gelss_solve", time only).
+ * Returns the
  * number of launches, their total device time in ms and the algorithmic flops
  * and bytes those launches were credited with. */
 int brd_profile_enable(int enable);

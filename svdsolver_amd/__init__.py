@@ -8,8 +8,9 @@ from .brd import (BRD_DEVICE_PTR, BRD_EXACT_ORDER, BRD_NO_EXTRACT, BRD_SIGMA, Br
                   band2bd, bdsvd, bdsvd_gpu, brd_p1, brd_p2, check_errors, cuda_brd_p1, ge2band, lib, profile_enable,
                   profile_query, profile_reset, reduce_many, release_stream, set_overlap, overlap_cus, singular_values,
                   singular_values_gpu, svd_batched, svd_mid_batched, svd_tall_batched, svdvals_batched, svdvals_mid_batched,
-                  svdvals_tall_batched, gesvd_batched, gesvdvals_batched)
+                  svdvals_tall_batched, gesvd_batched, gesvdvals_batched, lstsq_batched, pinv_batched, BRD_LS_TRANS)
 
 __all__ = ["ge2band", "band2bd", "reduce_many", "brd_p1", "brd_p2", "cuda_brd_p1", "bdsvd", "bdsvd_gpu", "singular_values",
            "singular_values_gpu", "svd_batched", "svdvals_batched", "svd_mid_batched", "svdvals_mid_batched", "svd_tall_batched",
-           "svdvals_tall_batched", "gesvd_batched", "gesvdvals_batched", "BrdError"]
+           "svdvals_tall_batched", "gesvd_batched", "gesvdvals_batched", "lstsq_batched", "pinv_batched",
+           "BrdError"]

@@ -34,6 +34,7 @@ BRD_COMPAT = 0x0
 BRD_EXACT_ORDER = 0x4
 BRD_NO_EXTRACT = 0x8
 BRD_SIGMA = 0x10
+BRD_LS_TRANS = 0x20
 
 EXPORTED = (
     "brd_ge2band_f64", "brd_ge2band_f32", "brd_band2bd_f64", "brd_band2bd_f32",
@@ -44,6 +45,7 @@ EXPORTED = (
     "brd_svd_batched_f64", "brd_svd_batched_f32", "brd_svd_mid_batched_f64", "brd_svd_mid_batched_f32",
     "brd_svd_tall_batched_work_bytes", "brd_svd_tall_batched_f64", "brd_svd_tall_batched_f32",
     "brd_gesvd_batched_work_bytes", "brd_gesvd_batched_f64", "brd_gesvd_batched_f32",
+    "brd_gelss_batched_work_bytes", "brd_gelss_batched_f64", "brd_gelss_batched_f32",
 )
 
 # brd_coll_fn (include/brd.h): int (*)(int op, const void *send, void *recv,
@@ -101,7 +103,11 @@ def _load() -> ctypes.CDLL:
         sg = getattr(L, f"brd_gesvd_batched_{t}")
         sg.argtypes = list(st.argtypes)
         sg.restype = ci
-    for q in (L.brd_svd_tall_batched_work_bytes, L.brd_gesvd_batched_work_bytes):
+        ls = getattr(L, f"brd_gelss_batched_{t}")
+        ls.argtypes = [vp, ci, ci, ci, ci, ctypes.c_long, vp, ci, ci, ctypes.c_long, vp, ci, ctypes.c_long,
+                       ctypes.c_double if t == "f64" else ctypes.c_float, vp, vp, vp, vp, ctypes.c_long, cu]
+        ls.restype = ci
+    for q in (L.brd_svd_tall_batched_work_bytes, L.brd_gesvd_batched_work_bytes, L.brd_gelss_batched_work_bytes):
         q.argtypes = [ci, ci, ci, ci, ci]
         q.restype = ctypes.c_long
     L.brd_set_stream.argtypes = [vp]
@@ -463,6 +469,118 @@ def gesvd_batched(A, *, compute_uv: bool = True, check: bool = True, sync: bool 
 def gesvdvals_batched(A, **kw):
     """Singular values only: ``gesvd_batched(A, compute_uv=False, **kw)``."""
     return gesvd_batched(A, compute_uv=False, **kw)
+
+
+# ---------------------------------------------------------------------------
+# batched least squares and pseudo-inverse from the batched SVD factors
+# ---------------------------------------------------------------------------
+def _gelss_batched_call(A, B, name, rcond, check, sync):
+    """brd_gelss_batched_*: the argument rules of :func:`_svd_batched_call` for
+    ``A`` (and ``B``), the outputs and the call.  ``B`` None: the identity.
+    Returns (X, rank, S, info), all with the batch dimension."""
+    import torch
+    if not _is_torch_cuda(A) or not (B is None or _is_torch_cuda(B)):
+        raise ValueError(f"{name} takes torch CUDA tensors")
+    if A.dim() not in (2, 3):
+        raise ValueError("A must be (batch, m, n) or (m, n)")
+    sfx = _sfx(A.dtype)
+    A3 = A.unsqueeze(0) if A.dim() == 2 else A
+    batch, m, n = A3.shape
+    if batch < 1 or m < 1 or n < 1:
+        raise ValueError(f"{name} needs batch, m, n >= 1")
+    rows_b, rows_x = m, n
+    flags = 0
+    if m < n:   # the C ABI keeps m >= n: A x = b is (A^T)^T x = b
+        A3 = A3.transpose(1, 2).contiguous()
+        m, n = n, m
+        flags |= BRD_LS_TRANS
+    if A3.stride(2) != 1 or A3.stride(1) < n or (batch > 1 and A3.stride(0) < (m - 1) * A3.stride(1) + n):
+        raise ValueError("A must have unit column stride, row stride >= n and non-overlapping matrices")
+    lda = int(A3.stride(1))
+    stride_a = int(A3.stride(0)) if batch > 1 else m * lda
+    if B is None:
+        nrhs, bptr, ldb, stride_b = rows_b, 0, 0, 0
+    else:
+        if B.dtype != A.dtype or B.device != A.device:
+            raise ValueError("B must have A's dtype and device")
+        if B.dim() != 3 or B.shape[0] != batch or B.shape[1] != rows_b or B.shape[2] < 1:
+            raise ValueError(f"B must hold {rows_b} rows per matrix of A")
+        nrhs = int(B.shape[2])
+        if B.stride(2) != 1 or B.stride(1) < nrhs or (batch > 1 and B.stride(0) < (rows_b - 1) * B.stride(1) + nrhs):
+            raise ValueError("B must have unit column stride, row stride >= its columns and non-overlapping matrices")
+        ldb = int(B.stride(1))
+        stride_b = int(B.stride(0)) if batch > 1 else rows_b * ldb
+        bptr = B.data_ptr()
+    need = int(lib.brd_gelss_batched_work_bytes(batch, m, n, nrhs, A.element_size()))
+    if need < 0:
+        raise BrdError("brd_gelss_batched_work_bytes", need, f"{m} x {n} matrices are not supported "
+                       "(at most 128 columns, or 128 rows for wide input)")
+    X = torch.empty((batch, rows_x, nrhs), dtype=A.dtype, device=A.device)
+    S = torch.empty((batch, n), dtype=A.dtype, device=A.device)
+    rank = torch.empty(batch, dtype=torch.int32, device=A.device)
+    info = torch.empty(batch, dtype=torch.int32, device=A.device)
+    wbuf = torch.empty(need, dtype=torch.uint8, device=A.device)   # lives until the call has run
+    _bind_stream(A)
+    fn = f"brd_gelss_batched_{sfx}"
+    wait = sync or check
+    _check(fn, getattr(lib, fn)(ctypes.c_void_p(A3.data_ptr()), batch, m, n, lda, stride_a,
+                                ctypes.c_void_p(bptr), nrhs, ldb, stride_b,
+                                ctypes.c_void_p(X.data_ptr()), nrhs, rows_x * nrhs,
+                                -1.0 if rcond is None else float(rcond),
+                                ctypes.c_void_p(S.data_ptr()), ctypes.c_void_p(rank.data_ptr()),
+                                ctypes.c_void_p(info.data_ptr()), ctypes.c_void_p(wbuf.data_ptr()), need,
+                                flags | (0 if wait else BRD_ASYNC)))
+    if check:
+        capped = torch.nonzero(info == 1).flatten().tolist()
+        if capped:
+            raise BrdError(fn, 1, f"sweep cap reached for matrices {capped}")
+    return X, rank, S, info
+
+
+def lstsq_batched(A, B, rcond=None, *, check: bool = True, sync: bool = True):
+    """Minimum-norm least-squares solutions of a batch of systems through the
+    batched SVD (brd_gelss_batched_*: :func:`gesvd_batched`'s launches and one
+    more that forms ``V diag(1/s) U^T B`` without writing the factors' products
+    to memory).  ``A`` is ``(batch, m, n)`` or ``(m, n)``, any number of rows
+    and at most 128 columns or the transpose of that; ``B`` is ``(batch, m,
+    k)`` or ``(batch, m)`` (``(m, k)`` or ``(m,)`` for a single matrix), both
+    float32/float64 torch CUDA tensors with contiguous rows; neither is
+    modified.
+
+    Singular values ``s_j <= rcond * s_1`` are treated as zero (``rcond``
+    None: ``max(m, n) * eps``, numpy's and torch's default).  Returns ``(X,
+    rank, S)``: ``X`` shaped like ``B`` with n rows, ``rank`` (int32) the
+    number of singular values kept per matrix, ``S`` the singular values
+    (descending).  A matrix holding a NaN or Inf gets NaN and rank -1.
+
+    ``check`` and ``sync`` are those of :func:`svd_batched`; with
+    ``check=False`` the per-matrix ``info`` tensor is appended."""
+    if not _is_torch_cuda(A) or not _is_torch_cuda(B):
+        raise ValueError("lstsq_batched takes torch CUDA tensors")
+    single = A.dim() == 2
+    vec = B.dim() == (1 if single else 2)
+    if B.dim() != A.dim() - (1 if vec else 0):
+        raise ValueError("B must be (batch, m, k) or (batch, m) for a batch, (m, k) or (m,) for one matrix")
+    B3 = B.unsqueeze(-1) if vec else B
+    B3 = B3.unsqueeze(0) if single else B3
+    X, rank, S, info = _gelss_batched_call(A, B3, "lstsq_batched", rcond, check, sync)
+    if vec:
+        X = X[..., 0]
+    if single:
+        X, rank, S, info = X[0], rank[0], S[0], info[0]
+    return (X, rank, S) if check else (X, rank, S, info)
+
+
+def pinv_batched(A, rcond=None, *, check: bool = True, sync: bool = True):
+    """Pseudo-inverses of a batch of matrices through the batched SVD
+    (brd_gelss_batched_* with the identity as right-hand side): ``A`` as for
+    :func:`lstsq_batched`; returns ``P`` of shape ``(batch, n, m)`` (or ``(n,
+    m)``) for either orientation, singular values ``s_j <= rcond * s_1``
+    treated as zero.  ``check=False`` appends the ``info`` tensor."""
+    X, _, _, info = _gelss_batched_call(A, None, "pinv_batched", rcond, check, sync)
+    if _is_torch_cuda(A) and A.dim() == 2:
+        X, info = X[0], info[0]
+    return X if check else (X, info)
 
 
 # ---------------------------------------------------------------------------

@@ -10,8 +10,10 @@
 #include <cstdio>
 #include <cstring>
 #include <deque>
+#include <limits>
 #include <map>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -851,18 +853,32 @@ static long gesvd_batched_work_bytes(int batch, int m, int n, int vectors, int e
     return gesvd_work_elems(batch, m, n, vectors) * elem_bytes;
 }
 
+// The size checks of a batch of m x n matrices (in gesvd_batched's order);
+// who: the entry point named in the message.
+static int gesvd_check_shape(const char *who, int batch, int m, int n, int lda, long stride_a) {
+    if (batch < 1) return fail(BRD_EINVAL, "%s: need batch >= 1 (batch=%d)", who, batch);
+    if (n < 1) return fail(BRD_EINVAL, "%s: need n >= 1 (n=%d)", who, n);
+    if (m < n) return fail(BRD_EINVAL, "%s: need m >= n (m=%d n=%d)", who, m, n);
+    if (lda < n) return fail(BRD_EINVAL, "%s: lda (%d) < n (%d)", who, lda, n);
+    if (stride_a < (long)(m - 1) * lda + n)
+        return fail(BRD_EINVAL, "%s: stride_a (%ld) < (m-1) lda + n", who, stride_a);
+    return BRD_OK;
+}
+
+// The launches of gesvd_batched on stream s, arguments checked and the lock
+// held by the caller.  kind: the profile kind of the whole call (nullptr: none).
+template <typename T>
+static int gesvd_batched_enqueue(const T *A, int batch, int m, int n, int lda, long stride_a, T *S, T *U, int ldu,
+                                 long stride_u, T *V, int ldv, long stride_v, int *info, void *work, const char *kind,
+                                 hipStream_t s);
+
 template <typename T>
 static int gesvd_batched(const T *A, int batch, int m, int n, int lda, long stride_a, T *S, T *U, int ldu,
                          long stride_u, T *V, int ldv, long stride_v, int *info, void *work, long work_bytes,
                          unsigned flags) {
     std::lock_guard<std::mutex> lk(g_ctx.mu);
     if (!A || !S || !info) return fail(BRD_EINVAL, "brd_gesvd_batched: A, S or info is NULL");
-    if (batch < 1) return fail(BRD_EINVAL, "brd_gesvd_batched: need batch >= 1 (batch=%d)", batch);
-    if (n < 1) return fail(BRD_EINVAL, "brd_gesvd_batched: need n >= 1 (n=%d)", n);
-    if (m < n) return fail(BRD_EINVAL, "brd_gesvd_batched: need m >= n (m=%d n=%d)", m, n);
-    if (lda < n) return fail(BRD_EINVAL, "brd_gesvd_batched: lda (%d) < n (%d)", lda, n);
-    if (stride_a < (long)(m - 1) * lda + n)
-        return fail(BRD_EINVAL, "brd_gesvd_batched: stride_a (%ld) < (m-1) lda + n", stride_a);
+    if (int rc = gesvd_check_shape("brd_gesvd_batched", batch, m, n, lda, stride_a)) return rc;
     if (U && (ldu < n || stride_u < (long)(m - 1) * ldu + n))
         return fail(BRD_EINVAL, "brd_gesvd_batched: ldu (%d) < n or stride_u (%ld) < (m-1) ldu + n", ldu, stride_u);
     if (V && (ldv < n || stride_v < (long)(n - 1) * ldv + n))
@@ -881,9 +897,22 @@ static int gesvd_batched(const T *A, int batch, int m, int n, int lda, long stri
         (need > 0 && !is_device_ptr(work)))
         return fail(BRD_EINVAL, "brd_gesvd_batched: A, S, U, V, info and work must be device memory");
     hipStream_t s = stream();
+    if (int rc = gesvd_batched_enqueue<T>(A, batch, m, n, lda, stride_a, S, U, ldu, stride_u, V, ldv, stride_v, info,
+                                          work, "gesvd_batched", s))
+        return rc;
+    if (!(flags & BRD_ASYNC)) HIP_TRY(hipStreamSynchronize(s));
+    return BRD_OK;
+}
+
+template <typename T>
+static int gesvd_batched_enqueue(const T *A, int batch, int m, int n, int lda, long stride_a, T *S, T *U, int ldu,
+                                 long stride_u, T *V, int ldv, long stride_v, int *info, void *work, const char *kind,
+                                 hipStream_t s) {
+    const long need = gesvd_work_elems(batch, m, n, U != nullptr) * (long)sizeof(T);
     {
         const double el = (double)batch * ((double)m * n + n + (U ? (double)m * n + (double)n * n : 0.0));
-        ProfScope ps("gesvd_batched", 0, el * sizeof(T) + (double)batch * sizeof(int), s);
+        std::optional<ProfScope> ps;   // the whole call's entry; none when a caller records its own
+        if (kind) ps.emplace(kind, 0, el * sizeof(T) + (double)batch * sizeof(int), s);
         const bool mid = n > 64;
         if (need == 0) {
             if (mid) {
@@ -922,6 +951,75 @@ static int gesvd_batched(const T *A, int batch, int m, int n, int lda, long stri
                     HIP_TRY(launch_qr_tall_apply<T>(UR, tau, info, batch, m, n, U, ldu, stride_u, s));
                 }
             }
+        }
+    }
+    return BRD_OK;
+}
+
+// Batched least squares / pseudo-inverse (brd_gelss_batched.hip after
+// gesvd_batched's launches with vectors): the factors U, V (and S) live in the
+// caller's workspace behind gesvd_batched's own, every piece 256-byte aligned.
+static long round256(long bytes) { return (bytes + 255) & ~255L; }
+
+static long gelss_batched_work_bytes(int batch, int m, int n, int nrhs, int elem_bytes) {
+    (void)nrhs;   // the solve launch keeps its n x 16 tile in LDS
+    const long w0 = gesvd_batched_work_bytes(batch, m, n, 1, elem_bytes);
+    if (w0 < 0) return w0;
+    return round256(w0) + round256((long)batch * m * n * elem_bytes) + round256((long)batch * n * n * elem_bytes) +
+           round256((long)batch * n * elem_bytes);
+}
+
+template <typename T>
+static int gelss_batched(const T *A, int batch, int m, int n, int lda, long stride_a, const T *B, int nrhs, int ldb,
+                         long stride_b, T *X, int ldx, long stride_x, T rcond, T *S, int *rank, int *info, void *work,
+                         long work_bytes, unsigned flags) {
+    std::lock_guard<std::mutex> lk(g_ctx.mu);
+    static const char *who = "brd_gelss_batched";
+    if (!A || !info) return fail(BRD_EINVAL, "%s: A or info is NULL", who);
+    if (int rc = gesvd_check_shape(who, batch, m, n, lda, stride_a)) return rc;
+    if (n > 128) return fail(BRD_EUNSUPPORTED, "%s: n = %d is beyond 128 columns", who, n);
+    const bool trans = (flags & BRD_LS_TRANS) != 0;
+    const int rows_b = trans ? n : m, rows_x = trans ? m : n;   // B: rows_b x nrhs, X: rows_x x nrhs
+    if (!B) nrhs = rows_b;                                      // the identity
+    if (nrhs < 1) return fail(BRD_EINVAL, "%s: need nrhs >= 1 (nrhs=%d)", who, nrhs);
+    if (B && (ldb < nrhs || stride_b < (long)(rows_b - 1) * ldb + nrhs))
+        return fail(BRD_EINVAL, "%s: ldb (%d) < nrhs (%d) or stride_b (%ld) < (rows-1) ldb + nrhs", who, ldb, nrhs,
+                    stride_b);
+    if (ldx < nrhs || stride_x < (long)(rows_x - 1) * ldx + nrhs)
+        return fail(BRD_EINVAL, "%s: ldx (%d) < %d columns or stride_x (%ld) < (rows-1) ldx + columns", who, ldx, nrhs,
+                    stride_x);
+    if (!X) return fail(BRD_EINVAL, "%s: X is NULL", who);
+    const long w0 = round256(gesvd_work_elems(batch, m, n, 1) * (long)sizeof(T));
+    const long wu = round256((long)batch * m * n * (long)sizeof(T));
+    const long wv = round256((long)batch * n * n * (long)sizeof(T));
+    const long need = w0 + wu + wv + round256((long)batch * n * (long)sizeof(T));
+    if (!work || work_bytes < need)
+        return fail(BRD_EINVAL, "%s: work is NULL or work_bytes (%ld) < %ld (brd_gelss_batched_work_bytes)", who,
+                    work_bytes, need);
+    if (((uintptr_t)work % 256) != 0) return fail(BRD_EINVAL, "%s: work is not aligned to 256 bytes", who);
+    if (!is_device_ptr(A) || !is_device_ptr(info) || !is_device_ptr(X) || !is_device_ptr(work) ||
+        (B && !is_device_ptr(B)) || (S && !is_device_ptr(S)) || (rank && !is_device_ptr(rank)))
+        return fail(BRD_EINVAL, "%s: A, B, X, S, rank, info and work must be device memory", who);
+    T *U = (T *)((char *)work + w0);
+    T *V = (T *)((char *)work + w0 + wu);
+    T *Sw = S ? S : (T *)((char *)work + w0 + wu + wv);
+    if (rcond < 0) rcond = (T)m * std::numeric_limits<T>::epsilon();   // max(m, n) eps: numpy's and torch's default
+    hipStream_t s = stream();
+    {
+        const double el = (double)batch * ((double)m * n + (B ? (double)rows_b * nrhs : 0.0) +
+                                           (double)rows_x * nrhs + (S ? n : 0));
+        ProfScope ps("gelss_batched", 0, el * sizeof(T), s);
+        const long mn = (long)m * n, nn = (long)n * n;
+        if (int rc = gesvd_batched_enqueue<T>(A, batch, m, n, lda, stride_a, Sw, U, n, mn, V, n, nn, info, work,
+                                              nullptr, s))
+            return rc;
+        ProfScope p2("gelss_solve", 0, 0, s);
+        if (trans) {
+            HIP_TRY(launch_gelss_solve<T>(V, n, n, nn, U, m, n, mn, Sw, n, rcond, B, nrhs, ldb, stride_b, X, ldx,
+                                          stride_x, rank, info, batch, s));
+        } else {
+            HIP_TRY(launch_gelss_solve<T>(U, m, n, mn, V, n, n, nn, Sw, n, rcond, B, nrhs, ldb, stride_b, X, ldx,
+                                          stride_x, rank, info, batch, s));
         }
     }
     if (!(flags & BRD_ASYNC)) HIP_TRY(hipStreamSynchronize(s));
@@ -1005,6 +1103,22 @@ int brd_gesvd_batched_f32(const float *A, int batch, int m, int n, int lda, long
                           long work_bytes, unsigned flags) {
     return brd::gesvd_batched<float>(A, batch, m, n, lda, stride_a, S, U, ldu, stride_u, V, ldv, stride_v, info, work,
                                      work_bytes, flags);
+}
+
+long brd_gelss_batched_work_bytes(int batch, int m, int n, int nrhs, int elem_bytes) {
+    return brd::gelss_batched_work_bytes(batch, m, n, nrhs, elem_bytes);
+}
+int brd_gelss_batched_f64(const double *A, int batch, int m, int n, int lda, long stride_a, const double *B, int nrhs,
+                          int ldb, long stride_b, double *X, int ldx, long stride_x, double rcond, double *S,
+                          int *rank, int *info, void *work, long work_bytes, unsigned flags) {
+    return brd::gelss_batched<double>(A, batch, m, n, lda, stride_a, B, nrhs, ldb, stride_b, X, ldx, stride_x, rcond,
+                                      S, rank, info, work, work_bytes, flags);
+}
+int brd_gelss_batched_f32(const float *A, int batch, int m, int n, int lda, long stride_a, const float *B, int nrhs,
+                          int ldb, long stride_b, float *X, int ldx, long stride_x, float rcond, float *S, int *rank,
+                          int *info, void *work, long work_bytes, unsigned flags) {
+    return brd::gelss_batched<float>(A, batch, m, n, lda, stride_a, B, nrhs, ldb, stride_b, X, ldx, stride_x, rcond,
+                                     S, rank, info, work, work_bytes, flags);
 }
 
 int brd_set_stream(void *hip_stream) {

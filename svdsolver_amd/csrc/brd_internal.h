@@ -156,6 +156,21 @@ template <typename T>
 hipError_t launch_qr_tall_mid_apply(T *UR, const T *tau, const int *info, int batch, int m, int n, T *U, long ldu,
                                     long stride_u, hipStream_t s);
 
+// Least squares from the batched SVD factors (brd_gelss_batched.hip): per
+// matrix X = R diag(sigma+) (L^T B), sigma+_j = 1 / sigma_j where sigma_j >
+// rcond sigma_1 and 0 elsewhere; rank (may be null) receives the number kept.
+// L = U, R = V: min |A x - b|; L = V, R = U: the minimum-norm solution of
+// A^T x = b.  B == nullptr: the identity (nrhs = rows_l).  Matrices with
+// info == 2 get NaN and rank -1.  One launch; n <= 128, else
+// hipErrorInvalidValue.
+template <typename T>
+hipError_t launch_gelss_solve(const T *L, int rows_l, long ldl, long stride_l,   // left factor, rows_l x n
+                              const T *R, int rows_r, long ldr, long stride_r,   // right factor, rows_r x n
+                              const T *S, int n, T rcond,
+                              const T *B, int nrhs, long ldb, long stride_b,     // rows_l x nrhs, or nullptr = identity
+                              T *X, long ldx, long stride_x,                     // rows_r x nrhs
+                              int *rank, const int *info, int batch, hipStream_t s);
+
 // ---- services of the C-ABI layer (brd_api.cpp) used by the distributed
 // driver (brd_dist.hip) ------------------------------------------------------
 int api_fail(int code, const char *msg);           // sets brd_last_error, returns code

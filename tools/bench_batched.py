@@ -39,6 +39,15 @@ profiles/batched_svd_tall_mid.json): values and vectors, the stage shares, the
 values path's HBM rate, torch as above, and the loop of singular_values_gpu
 over 64 of the matrices padded with zero columns to m x m (the only way the
 two-stage path takes them; shapes of at most 512 rows).
+
+--lstsq times the batched least squares (lstsq_batched, pinv_batched) instead,
+by the same method, at batch x m x n = 1024x512x128, 1024x256x72, 1024x128x64
+and 256x4096x128 (default output profiles/batched_lstsq.json): lstsq_batched at
+1 and 16 right-hand sides and pinv_batched; the share of the solve launch in
+the call (profile kinds gelss_solve over gelss_batched, ten calls);
+gesvd_batched with vectors at the same shape (the cost before the solve);
+gesvd_batched followed by the equivalent chain of torch.bmm calls with the
+same cutoff; torch.linalg.lstsq / pinv on the first 128 matrices.
 """
 import argparse
 import json
@@ -59,6 +68,8 @@ SHAPES = [(16384, 16, 16), (4096, 32, 32), (2048, 64, 64), (1024, 128, 64)]
 TALL_SHAPES = [(4096, 256, 16), (1024, 1024, 32), (256, 4096, 64), (1024, 512, 64)]
 MID_SHAPES = [(1024, 96, 96), (1024, 128, 96), (1024, 128, 128)]
 TALL_MID_SHAPES = [(1024, 512, 96), (1024, 512, 128), (256, 4096, 128), (1024, 256, 72)]
+LSTSQ_SHAPES = [(1024, 512, 128), (1024, 256, 72), (1024, 128, 64), (256, 4096, 128)]
+LSTSQ_NRHS = (1, 16)
 LOOP_MAX_ROWS = 512   # the two-stage loop pads to m x m
 WINDOW_S, REPEATS, LOOP_MATRICES = 0.3, 5, 64
 TORCH_SUBSET, TORCH_CALL_S, STAGE_CALLS = 128, 1.0, 10
@@ -177,6 +188,81 @@ def tall_mid_rows(args, dev, result):
                 f.write("\n")
 
 
+def solve_share(fn):
+    """Share of the solve launch in the device time of STAGE_CALLS calls."""
+    torch.cuda.synchronize()
+    S.profile_enable(True)
+    S.profile_reset()
+    for _ in range(STAGE_CALLS):
+        fn()
+    torch.cuda.synchronize()
+    solve, whole = S.profile_query("gelss_solve")["ms"], S.profile_query("gelss_batched")["ms"]
+    S.profile_enable(False)
+    return {"solve_share": solve / whole, "solve_us": solve * 1e3 / STAGE_CALLS, "call_us": whole * 1e3 / STAGE_CALLS}
+
+
+def bmm_chain(A, B, rcond):
+    """What a user of gesvd_batched writes: the cutoff by hand and a chain of
+    torch.bmm calls.  B None: the pseudo-inverse."""
+    U, Sv, Vh = S.gesvd_batched(A, check=False, sync=False)[:3]
+    keep = Sv > rcond * Sv[:, :1]
+    inv = torch.where(keep, 1 / Sv, torch.zeros_like(Sv))
+    Ut = U.transpose(1, 2)
+    C = Ut if B is None else torch.bmm(Ut, B)
+    return torch.bmm(Vh.transpose(1, 2), inv.unsqueeze(2) * C)
+
+
+def torch_row(fn, count):
+    try:
+        return per_matrix(measure(fn), count)
+    except RuntimeError as e:   # a torch build without the batched solver behind this call
+        return {"error": str(e).splitlines()[0][:200]}
+
+
+def lstsq_rows(args, dev, result):
+    for dt in (torch.float64, torch.float32):
+        for batch, m, n in LSTSQ_SHAPES:
+            g = torch.Generator(device=dev).manual_seed(1234)
+            A = torch.rand((batch, m, n), dtype=dt, device=dev, generator=g) * 5
+            row = {"dtype": str(dt).replace("torch.", ""), "batch": batch, "m": m, "n": n}
+            rcond = max(m, n) * torch.finfo(dt).eps
+            info = S.gesvd_batched(A, check=False)[3]
+            row["info_nonzero"] = int((info != 0).sum())
+            row["gesvd_batched_vectors"] = per_matrix(
+                measure(lambda: S.gesvd_batched(A, check=False, sync=False)), batch)
+            At = A[:TORCH_SUBSET]
+            for k in LSTSQ_NRHS:
+                B = torch.rand((batch, m, k), dtype=dt, device=dev, generator=g) * 2 - 1
+                X, rank = S.lstsq_batched(A, B, check=False)[:2]
+                Xc = bmm_chain(A, B, rcond)
+                r = {"rank_min": int(rank.min()),
+                     "max_diff_to_chain": float((X - Xc).abs().max() / Xc.abs().max())}
+                r["lstsq_batched"] = per_matrix(measure(lambda: S.lstsq_batched(A, B, check=False, sync=False)), batch)
+                r.update(solve_share(lambda: S.lstsq_batched(A, B, check=False, sync=False)))
+                r["gesvd_plus_bmm_chain"] = per_matrix(measure(lambda: bmm_chain(A, B, rcond)), batch)
+                r["chain_over_lstsq"] = r["gesvd_plus_bmm_chain"]["median_us"] / r["lstsq_batched"]["median_us"]
+                r["lstsq_over_gesvd"] = r["lstsq_batched"]["median_us"] / row["gesvd_batched_vectors"]["median_us"]
+                if not args.skip_torch:
+                    Bt = B[:TORCH_SUBSET]
+                    r["torch_batch"] = At.shape[0]
+                    r["torch_lstsq"] = torch_row(lambda: torch.linalg.lstsq(At, Bt), At.shape[0])
+                row[f"nrhs_{k}"] = r
+            r = {"pinv_batched": per_matrix(measure(lambda: S.pinv_batched(A, check=False, sync=False)), batch)}
+            r.update(solve_share(lambda: S.pinv_batched(A, check=False, sync=False)))
+            r["gesvd_plus_bmm_chain"] = per_matrix(measure(lambda: bmm_chain(A, None, rcond)), batch)
+            r["chain_over_pinv"] = r["gesvd_plus_bmm_chain"]["median_us"] / r["pinv_batched"]["median_us"]
+            if not args.skip_torch:
+                r["torch_batch"] = At.shape[0]
+                r["torch_pinv"] = torch_row(lambda: torch.linalg.pinv(At), At.shape[0])
+            row["pinv"] = r
+            result["rows"].append(row)
+            print(json.dumps(row), flush=True)
+            os.makedirs(os.path.dirname(args.out), exist_ok=True)
+            with open(args.out, "w") as f:   # rewritten after every shape: a cut-short run keeps its rows
+                json.dump(result, f, indent=1)
+                f.write("\n")
+
+
 def mid_rows(args, dev, result):
     for dt in (torch.float64, torch.float32):
         for batch, m, n in MID_SHAPES:
@@ -220,12 +306,14 @@ def main():
     ap.add_argument("--mid", action="store_true", help="the 65..128-column shapes through svd_mid_batched")
     ap.add_argument("--tall-mid", action="store_true",
                     help="more than 128 rows with 65..128 columns through gesvd_batched")
+    ap.add_argument("--lstsq", action="store_true", help="lstsq_batched and pinv_batched")
     args = ap.parse_args()
-    if args.tall + args.mid + args.tall_mid > 1:
-        ap.error("--tall, --mid and --tall-mid are separate runs")
+    if args.tall + args.mid + args.tall_mid + args.lstsq > 1:
+        ap.error("--tall, --mid, --tall-mid and --lstsq are separate runs")
     if args.out is None:
         name = ("batched_svd_tall.json" if args.tall else "batched_svd_mid.json" if args.mid else
-                "batched_svd_tall_mid.json" if args.tall_mid else "batched_svd.json")
+                "batched_svd_tall_mid.json" if args.tall_mid else "batched_lstsq.json" if args.lstsq else
+                "batched_svd.json")
         args.out = os.path.join(REPO, "profiles", name)
     args.out = os.path.abspath(args.out)
     dev = torch.device("cuda:0")
@@ -240,6 +328,9 @@ def main():
         return
     if args.tall_mid:
         tall_mid_rows(args, dev, result)
+        return
+    if args.lstsq:
+        lstsq_rows(args, dev, result)
         return
     for dt in (torch.float64, torch.float32):
         for batch, m, n in SHAPES:
